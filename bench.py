@@ -9,8 +9,16 @@ decompressed (Fp / Fp2 square root + sign rule), subgroup-checked and emitted as
 `serialize_uncompressed` bytes — and, for N > 1 GPUs, all-gathered over RCCL into one contiguous
 arkworks buffer on every rank (strong scaling: the transcript is fixed, ranks split it).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run does only what the headline needs: it generates the transcript, warms up, times the K
+steps and prints the line (with the roofline / valu / field_ops views of those same steps).
+`--full` adds everything else, as the line carried it before the option existed: the bit-exact
+verification and the oracle sample check of the output, `next_rows` (config 5, the loader /
+transcode / config 3 / host-API / end-to-end / drop-in binary rows) and `cpu_baseline`; the
+`--no-*` switches below trim a `--full` run. `--dump-outputs DIR` writes what the last timed step
+left in the output buffers (dump_outputs) as DIR/<name>.npy, so two builds can be compared.
 
 `--gpus N > 1` without a launcher starts `torch.distributed.run` itself, as a CHILD process,
 before anything touches the GPU, forwards rank 0's JSON line and exits with the child's code;
@@ -90,7 +98,15 @@ def parse():
                     help="skip the drop-in binaries' wall-clock rows (next_rows.cli_preprocess_*)")
     ap.add_argument("--no-host-api", dest="host_api", action="store_false",
                     help="skip the host-buffer FFI rows (next_rows.host_api)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the output (generator + C oracle sample) and measure next_rows and "
+                         "cpu_baseline; without it only the headline's steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (dump_outputs)")
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.no_verify = args.no_next_rows = args.no_cpu_baseline = True
+    return args
 
 
 def oracle_lib():
@@ -700,6 +716,42 @@ def oracle_sample_check(stream, runs):
             "equal": bool(ok), "seconds": time.perf_counter() - t}
 
 
+DUMP_SEED = 0xD0B5                           # the record sample of --dump-outputs
+DUMP_RECORDS = {"g1": 1 << 16, "g2": 1 << 14}  # 25 MB + 12.6 MB of float32 at 96 / 192 bytes per record
+DUMP_BLOCKS = 4096
+
+
+def dump_outputs(path, streams):
+    """--dump-outputs: what the last timed step left in each stream's output buffer (the arkworks
+    records a caller of the `_dev` entry points receives), as float .npy files, under 40 MB in all.
+    Per stream <kind>: `<kind>_record_index` (float64) is a seeded sample of at most
+    DUMP_RECORDS[kind] record indices, the first and the last record among them (the same for the
+    same sizes, whatever the build); `<kind>_records` (float32, sample x record bytes) holds those
+    records' bytes; `<kind>_block_bytesum` (float64, exact) the byte sums of the WHOLE buffer cut
+    into at most DUMP_BLOCKS equal slices, so every byte of a 12 GiB output counts. `first_bad`
+    (float64, one per stream) is the first rejected point's key, -1 when every point passed."""
+    import math
+
+    import numpy as np
+    import torch
+    from kzgpot import dist as KD
+
+    os.makedirs(path, exist_ok=True)
+    for s in streams:
+        n = s.out.numel() // s.rout
+        rng = np.random.default_rng(DUMP_SEED)
+        k = DUMP_RECORDS[s.kind]  # every record of a small stream, else k draws (repeats dropped) with both ends
+        idx = np.arange(n) if n <= k else np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, k - 2)]))
+        rec = s.out.view(n, s.rout).index_select(0, torch.from_numpy(idx).to(s.out.device))
+        np.save(os.path.join(path, f"{s.kind}_record_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(path, f"{s.kind}_records.npy"), rec.cpu().numpy().astype(np.float32))
+        rows = s.out.view(math.gcd(n, DUMP_BLOCKS), -1)
+        sums = [rows[i:i + 64].sum(1, dtype=torch.int64) for i in range(0, rows.shape[0], 64)]  # 64: bounded temporaries
+        np.save(os.path.join(path, f"{s.kind}_block_bytesum.npy"), torch.cat(sums).cpu().numpy().astype(np.float64))
+    keys = [s.bad_key() for s in streams]
+    np.save(os.path.join(path, "first_bad.npy"), np.array([-1.0 if k == KD.NO_BAD else float(k) for k in keys]))
+
+
 def host_api_rows(seed, dev, D, g1_log2=25, g2_log2=20):
     """The FFI boundary the Rust caller binds (include/kzgpot.h): kzgpot_g1_decompress /
     kzgpot_g2_decompress on PAGEABLE host buffers, as `read_g1` x N is replaced
@@ -1107,6 +1159,8 @@ def main():
     elapsed, ev, verified = timed([g1, g2], args.steps, args.warmup, world, dev, verify)
     clock = LAST_CLOCK.get("mhz")
     bad = KD.allreduce_min_key(min(g1.bad_key(), g2.bad_key()), dev) if world > 1 else min(g1.bad_key(), g2.bad_key())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [g1, g2])
     sample = None
     if verify and rank == 0 and (gather or world == 1):
         sample = oracle_sample_check(g1, args.oracle_sample_runs)

@@ -157,3 +157,18 @@ def test_num_cpus_follows_num_cpus_1_13(tmp_path):
     cg.write_text("0::/\n")  # cgroup v2 only
     assert b.cgroup_v1_cpu_quota(str(cg), str(mi)) is None
     assert b.num_cpus() == min(b.cgroup_v1_cpu_quota() or b.affinity_cpus(), b.affinity_cpus())
+
+
+def test_plain_run_measures_the_headline_only(monkeypatch):
+    """Without --full the verification, next_rows (the drop-in binaries' rows with them) and
+    cpu_baseline are off whatever else is given; --full restores the line as it was, trimmed by
+    the --no-* switches."""
+    b = load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = b.parse()
+    assert a.no_verify and a.no_next_rows and a.no_cpu_baseline
+    assert (a.steps, a.warmup, a.dump_outputs, a.full) == (5, 2, None, False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline", "--dump-outputs", "d"])
+    a = b.parse()
+    assert not a.no_verify and not a.no_next_rows and a.no_cpu_baseline and a.cli and a.host_api
+    assert a.dump_outputs == "d"

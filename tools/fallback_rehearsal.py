@@ -2,7 +2,7 @@
 kzgpot_decode_allgather_dev call raises (as a failing RCCL call would), the bench must finish
 verified on the torch path and say so in config.gather_impl. Run at one rank with --gather-at-1:
 
-    python tools/fallback_rehearsal.py --gather-at-1 --steps 1 --no-next-rows --no-cpu-baseline
+    python tools/fallback_rehearsal.py --full --gather-at-1 --steps 1 --no-next-rows --no-cpu-baseline
 """
 import os
 import sys

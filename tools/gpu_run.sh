@@ -9,8 +9,8 @@
 #   pytest        the whole GPU suite (pytest -m gpu)
 #   quicktests    the CLI, C-ABI stream and preprocess GPU tests only
 #   smoke         __graft_entry__.smoke()
-#   bench         python bench.py (the default line: config 4 + every row + cpu_baseline)
-#   bench_quick   bench.py without the CPU baseline and the e2e rows (kernel numbers only)
+#   bench         python bench.py --full (config 4, verified, + every row + cpu_baseline)
+#   bench_quick   bench.py --full without the CPU baseline and the e2e rows (kernel numbers only)
 #   stages        e2e stage trace: rocprofv3 marker + kernel + memory-copy trace of
 #                 tools/e2e_breakdown.py, summarised by tools/stage_summary.py
 #   codec_stalls  per-wave stall split of the G1 / G2 codec kernels (tools/pmc_codec_stalls.sh)
@@ -18,13 +18,13 @@
 #   asan          tools/asan_gpu_tests.sh (host-ASan library under the C-ABI GPU tests)
 #   loader_stalls tools/pmc_loader_stalls.sh
 #   loader_ceiling tools/microbench/bin/loader_ceiling (the loader's pattern variants, TB/s)
-#   gloo2         bench.py --gpus 2 --dist-backend gloo (the N > 1 launch path on one GPU)
-#   gloo8         bench.py --gpus 8 --dist-backend gloo at reduced sizes: the driver's world-8 control
+#   gloo2         bench.py --full --gpus 2 --dist-backend gloo (the N > 1 launch path on one GPU)
+#   gloo8         bench.py --full --gpus 8 --dist-backend gloo at reduced sizes: the driver's world-8 control
 #                 flow (8 spawned ranks, the rendezvous-store wait, rank 0's e2e at 8 shards, the exit
 #                 code) on the one GPU of the box
 #   overlap       tools/overlap_probe.py (copies on a second stream beside a codec launch, normal and
 #                 highest stream priority: do RCCL-like copy kernels progress during the decode?)
-#   gather1       bench.py --gather-at-1 (the library's RCCL path at one rank)
+#   gather1       bench.py --full --gather-at-1 (the library's RCCL path at one rank)
 #   port          tests/test_gpu_oracle_port.py alone (every point vs the GPU port of the oracle)
 #   campaign      tools/random_campaign.py for 9 minutes (SEED0=... for fresh seeds)
 #   campaign_g2   the same on the G2 ops only, with fresh seeds
@@ -46,8 +46,8 @@ for step in "$@"; do
     quicktests) timeout -k 10 600 python -u -m pytest tests/test_cli_gpu.py tests/test_gpu_capi_stream.py \
                   tests/test_gpu_preprocess.py -x -v --timeout 300 --timeout-method thread > ${o}_quicktests.txt 2>&1 ;;
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > ${o}_smoke.txt 2>&1 ;;
-    bench) timeout -k 10 600 python -u bench.py > ${o}_bench_n1.json 2> ${o}_bench.err ;;
-    bench_quick) timeout -k 10 400 python -u bench.py --no-cpu-baseline --e2e-log2 0 --no-host-api \
+    bench) timeout -k 10 600 python -u bench.py --full > ${o}_bench_n1.json 2> ${o}_bench.err ;;
+    bench_quick) timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --e2e-log2 0 --no-host-api \
                    > ${o}_bench_quick.json 2> ${o}_bench_quick.err ;;
     stages) timeout -k 10 400 rocprofv3 --marker-trace --kernel-trace --memory-copy-trace --output-format csv \
               -d ${o}_stages -o run -- python3 tools/e2e_breakdown.py > ${o}_stages_calls.json 2> ${o}_stages.err &&
@@ -58,14 +58,14 @@ for step in "$@"; do
     asan) timeout -k 10 700 bash tools/asan_gpu_tests.sh ;;
     loader_ceiling) timeout -k 10 400 tools/microbench/bin/loader_ceiling > ${o}_loader_ceiling.txt 2>&1 ;;
     loader_stalls) timeout -k 10 400 bash tools/pmc_loader_stalls.sh ;;
-    gloo2) timeout -k 10 400 python bench.py --gpus 2 --dist-backend gloo --g1-log2 24 --steps 2 --warmup 1 \
+    gloo2) timeout -k 10 400 python bench.py --full --gpus 2 --dist-backend gloo --g1-log2 24 --steps 2 --warmup 1 \
              --bn254-log2 0 --no-cpu-baseline > ${o}_bench_gloo2.json 2> ${o}_bench_gloo2.err ;;
-    gloo8) t0=$(date +%s%N); timeout -k 10 600 python bench.py --gpus 8 --dist-backend gloo --g1-log2 23 --g2-log2 13 \
+    gloo8) t0=$(date +%s%N); timeout -k 10 600 python bench.py --full --gpus 8 --dist-backend gloo --g1-log2 23 --g2-log2 13 \
              --steps 2 --warmup 1 --bn254-log2 23 --e2e-log2 18 --no-cpu-baseline > ${o}_bench_gloo8.json \
              2> ${o}_bench_gloo8.err; rc=$?; echo "wall_ms $(( ($(date +%s%N) - t0) / 1000000 )) rc $rc" \
              > ${o}_bench_gloo8.wall; (exit $rc) ;;
     overlap) timeout -k 10 180 python -u tools/overlap_probe.py > ${o}_overlap.json 2> ${o}_overlap.err ;;
-    gather1) timeout -k 10 400 python bench.py --gather-at-1 --steps 2 --no-cpu-baseline --no-next-rows \
+    gather1) timeout -k 10 400 python bench.py --full --gather-at-1 --steps 2 --no-cpu-baseline --no-next-rows \
                > ${o}_bench_gather_at_1.json 2> ${o}_bench_gather_at_1.err ;;
     port) timeout -k 10 1000 python -u -m pytest tests/test_gpu_oracle_port.py -x -v --timeout 900 \
             --timeout-method thread --durations=0 > ${o}_pytest_port.txt 2>&1 ;;

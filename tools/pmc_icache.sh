@@ -12,7 +12,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 rocprofv3 -L > "$out/avail.txt" 2>&1 || true
 grep -oE "SQC?_[A-Z_]*(ICACHE|IFETCH|WAIT_INST|INST_LEVEL)[A-Z_]*" "$out/avail.txt" | sort -u > "$out/icache_counters.txt" || true
-step="bench.py --steps 1 --warmup 0 --no-verify --no-cpu-baseline --bn254-log2 0 --e2e-log2 0 --g1-log2 22"
+step="bench.py --full --steps 1 --warmup 0 --no-verify --no-cpu-baseline --bn254-log2 0 --e2e-log2 0 --g1-log2 22"
 i=0
 for lib in "${libs[@]}"; do
   i=$((i + 1))
