@@ -1,5 +1,5 @@
 // Internal C++ interface between the C ABI (capi.hip) and the kernels (codec_kernels.hip,
-// g1_kernels.hip).
+// g1_kernels.hip; the device functions those two share are in codec_parts.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,6 +9,7 @@
 namespace kzgpot {
 
 constexpr int kBlock = 256;  // 4 waves; one point per lane
+inline unsigned grid_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }  // blocks for n points
 
 // G1Phase1 / G2Phase1: read_g1 / read_g2 straight into the in-memory GroupAffine (load_phase1) —
 // the transcode kernel in place on the input staging buffer, then the loader kernel. Host-buffer

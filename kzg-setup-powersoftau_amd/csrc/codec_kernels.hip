@@ -18,6 +18,11 @@
 //                              subgroup — in place on phase 1's output (Src = ArkInPlace), or on a
 //                              pairing-uncompressed input for the read_g1/read_g2 transcode
 //                              (Src = PairingBE). Rejected records are zero-filled.
+// The rules of both phases that G1 and G2 share — the compressed header (g1_head / g2_head), the
+// sign rule (sign_rule), the SWFlags parse (ark_sw_flags), the infinity / poison / zero record
+// (emit_no_point, store_ark_last) — and the subgroup tests on an LDS-parked point (g1_in_subgroup,
+// g2_in_subgroup) are stated once, in codec_parts.hpp; a kernel is a sequence of those calls plus
+// what it parks where and when it emits.
 // Splitting the phases keeps each kernel's live register set to one algorithm (the square-root
 // table or the scalar-multiplication state, not both); the extra traffic is one 96/192-B re-read
 // per point, against ~1,500 Fp multiplies of work. For G1 the fused kernel parks x and y in LDS
@@ -34,9 +39,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "codec.hpp"
-#include "curve.hpp"
-#include "records.hpp"
+#include "codec_parts.hpp"
 
 namespace kzgpot {
 
@@ -91,6 +94,19 @@ KZG_DEV void g2_rhs(fp2& r, const fp2& x) {
   fp_add_red(r.c1, r.c1, four);
 }
 
+// The ark record of a finite point in one go: x's canonical words wait in LDS across the square
+// root (x.c0 in rows 0.., x.c1 in rows 12..; no HBM re-read), yc is the chosen root, canonical.
+KZG_DEV void emit_g2(uint4* dst, const uint32_t (*xwords)[kBlock], const fp2& yc) {
+  words w0, w1;
+  const uint32_t lane = lds_lane();
+  lds_load(w0, xwords, lane);
+  lds_load(w1, xwords + 12, lane);
+  store_words(dst, w0);
+  store_words(dst + 3, w1);
+  store_canon(dst + 6, yc.c0);
+  store_canon(dst + 9, yc.c1);
+}
+
 __global__ void __launch_bounds__(kBlock) k_g2_decompress(const uint4* __restrict__ in, uint4* __restrict__ out,
                                                           uint64_t n, uint32_t flags,
                                                           unsigned long long* __restrict__ first_bad,
@@ -99,73 +115,31 @@ __global__ void __launch_bounds__(kBlock) k_g2_decompress(const uint4* __restric
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   const bool checked = !(flags & KZGPOT_NO_SUBGROUP_CHECK);
-  int st = 0;
-  bool is_inf, greatest;
+  wire_head_t h;
   fp2 a;
   {
     words w1, w0;  // wire order: x.c1 ‖ x.c0
     load_be(w1, in + i * 6);
     load_be(w0, in + i * 6 + 3);
-    const uint32_t b0 = w1[11] >> 24;
-    uint32_t rest = w0[11];
-#pragma unroll
-    for (int k = 0; k < 11; k++) rest |= w1[k] | w0[k];
-    const bool inf_clean = ((w1[11] & 0x3fffffffu) | rest) == 0;
-    w1[11] &= 0x1fffffffu;
-    if (!(b0 & 0x80u)) st = 1;
-    else if (b0 & 0x40u) st = inf_clean ? (checked ? 7 : 0) : 2;
-    else if (words_geq_p(w0) || words_geq_p(w1)) st = 3;
-    is_inf = (b0 & 0xc0u) == 0xc0u && st == 0;
-    greatest = (b0 & 0x20u) != 0;
-#pragma unroll
-    for (int k = 0; k < 12; k++) xpark[k][threadIdx.x] = w0[k], xpark[12 + k][threadIdx.x] = w1[k];
+    h = g2_head(w1, w0, checked);
+    lds_park(xpark, w0);
+    lds_park(xpark + 12, w1);
     fp2 x;
     words_to_mont(x.c0, w0);
     words_to_mont(x.c1, w1);
     g2_rhs(a, x);
   }
-  fp2 y;
+  int st = h.st;
+  fp2 y, yc;
   const bool on = fp2_sqrt(y, a);
-  if (st == 0 && !is_inf && !on) st = 4;
-
-  // pairing Ord for Fq2: lexicographic, c1 first
-  fp2 yc, nyc;
-  fp_from_mont(yc.c0, y.c0);
-  fp_from_mont(yc.c1, y.c1);
-  fp_neg_canon(nyc.c0, yc.c0);
-  fp_neg_canon(nyc.c1, yc.c1);
-  bool c1eq = true;
-#pragma unroll
-  for (int k = 0; k < NL; k++) c1eq = c1eq && (yc.c1.v[k] == nyc.c1.v[k]);
-  const bool lt = c1eq ? fp_lt_canon(yc.c0, nyc.c0) : fp_lt_canon(yc.c1, nyc.c1);
-  const bool keep = lt ^ greatest;
+  if (st == 0 && !h.is_inf && !on) st = 4;
+  sign_rule(yc, y, h.greatest);
 
   uint4* dst = out + i * 12;
-  if (st == 0 && !is_inf) {
-    words w1, w0;
-    uint32_t lane = threadIdx.x;
-    asm volatile("" : "+v"(lane));
-#pragma unroll
-    for (int k = 0; k < 12; k++) w0[k] = xpark[k][lane], w1[k] = xpark[12 + k][lane];
-    fp_select(yc.c0, keep, yc.c0, nyc.c0);
-    fp_select(yc.c1, keep, yc.c1, nyc.c1);
-    store_words(dst, w0);
-    store_words(dst + 3, w1);
-    store_canon(dst + 6, yc.c0);
-    store_canon(dst + 9, yc.c1);
-  } else {
-    words z, zx, zy0, zy1;
-    zero_words(z);
-    zero_words(zx);
-    zero_words(zy0);
-    zero_words(zy1);
-    if (is_inf) zy0[0] = 1, zy1[11] = 0x40000000u;  // ark zero() = ((0,0), (1,0), inf)
-    if (st && checked) zx[11] = kPoison;
-    store_words(dst, zx);
-    store_words(dst + 3, z);
-    store_words(dst + 6, zy0);
-    store_words(dst + 9, zy1);
-  }
+  if (st == 0 && !h.is_inf)
+    emit_g2(dst, xpark, yc);
+  else
+    emit_no_point<2>(dst, h.is_inf, st && checked);
   report(i, st, first_bad, status);
 }
 
@@ -183,86 +157,38 @@ k_g2_codec(const uint4* __restrict__ in, uint4* __restrict__ out, uint64_t n, ui
   __shared__ uint32_t base[4 * NL][kBlock];  // x.c0, x.c1, y.c0, y.c1 (Montgomery), limb-major
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
-  int st = 0;
-  bool greatest;
+  wire_head_t h;
   uint4* dst = out + i * 12;
   fp2 a;
   {
     words w1, w0;  // wire order: x.c1 ‖ x.c0
     load_be(w1, in + i * 6);
     load_be(w0, in + i * 6 + 3);
-    const uint32_t b0 = w1[11] >> 24;
-    uint32_t rest = w0[11];
-#pragma unroll
-    for (int k = 0; k < 11; k++) rest |= w1[k] | w0[k];
-    const bool inf_clean = ((w1[11] & 0x3fffffffu) | rest) == 0;
-    w1[11] &= 0x1fffffffu;
-    if (!(b0 & 0x80u)) st = 1;
-    else if (b0 & 0x40u) st = inf_clean ? 7 : 2;  // checked stream: infinity is rejected
-    else if (words_geq_p(w0) || words_geq_p(w1)) st = 3;
-    greatest = (b0 & 0x20u) != 0;
-#pragma unroll
-    for (int k = 0; k < 12; k++) base[2 * NL + k][threadIdx.x] = w0[k], base[2 * NL + 12 + k][threadIdx.x] = w1[k];
+    h = g2_head(w1, w0, true);  // checked stream: infinity is rejected
+    lds_park(base + 2 * NL, w0);
+    lds_park(base + 2 * NL + 12, w1);
     fp2 x;
     words_to_mont(x.c0, w0);
     words_to_mont(x.c1, w1);
-#pragma unroll
-    for (int k = 0; k < NL; k++) base[k][threadIdx.x] = x.c0.v[k], base[NL + k][threadIdx.x] = x.c1.v[k];
+    lds_park(base, x.c0.v);
+    lds_park(base + NL, x.c1.v);
     g2_rhs(a, x);
   }
+  int st = h.st;
   {
-    fp2 y;
+    fp2 y, yc;
     const bool on = fp2_sqrt(y, a);
     if (st == 0 && !on) st = 4;
-    fp2 yc, nyc;
-    fp_from_mont(yc.c0, y.c0);
-    fp_from_mont(yc.c1, y.c1);
-    fp_neg_canon(nyc.c0, yc.c0);
-    fp_neg_canon(nyc.c1, yc.c1);
-    bool c1eq = true;
-#pragma unroll
-    for (int k = 0; k < NL; k++) c1eq = c1eq && (yc.c1.v[k] == nyc.c1.v[k]);
-    const bool keep = (c1eq ? fp_lt_canon(yc.c0, nyc.c0) : fp_lt_canon(yc.c1, nyc.c1)) ^ greatest;
+    const bool keep = sign_rule(yc, y, h.greatest);
     if (st == 0) {
-      words w0, w1;
-      uint32_t lane = threadIdx.x;
-      asm volatile("" : "+v"(lane));
-#pragma unroll
-      for (int k = 0; k < 12; k++) w0[k] = base[2 * NL + k][lane], w1[k] = base[2 * NL + 12 + k][lane];
-      fp_select(yc.c0, keep, yc.c0, nyc.c0);
-      fp_select(yc.c1, keep, yc.c1, nyc.c1);
-      store_words(dst, w0);
-      store_words(dst + 3, w1);
-      store_canon(dst + 6, yc.c0);
-      store_canon(dst + 9, yc.c1);
-      // the chosen root in Montgomery form for the ladder: y's representative made canonical, or
-      // its negation p - y (0 -> 0), instead of converting the canonical bytes back (two multiplies)
-      fp m;
-      fp_reduce_once(y.c0, y.c0);
-      fp_neg_canon(m, y.c0);
-      fp_select(y.c0, keep, y.c0, m);
-      fp_reduce_once(y.c1, y.c1);
-      fp_neg_canon(m, y.c1);
-      fp_select(y.c1, keep, y.c1, m);
-#pragma unroll
-      for (int k = 0; k < NL; k++) base[2 * NL + k][threadIdx.x] = y.c0.v[k], base[3 * NL + k][threadIdx.x] = y.c1.v[k];
+      emit_g2(dst, base + 2 * NL, yc);
+      chosen_root_mont(y.c0, keep);
+      chosen_root_mont(y.c1, keep);
+      lds_park(base + 2 * NL, y.c0.v);
+      lds_park(base + 3 * NL, y.c1.v);
     }
   }
-  if (st == 0) {
-    auto load = [&](fp2& bx, fp2& by) {
-      uint32_t lane = threadIdx.x;
-      asm volatile("" : "+v"(lane));  // opaque index: re-read at every use, never hoisted
-#pragma unroll
-      for (int k = 0; k < NL; k++) {
-        bx.c0.v[k] = base[k][lane];
-        bx.c1.v[k] = base[NL + k][lane];
-        by.c0.v[k] = base[2 * NL + k][lane];
-        by.c1.v[k] = base[3 * NL + k][lane];
-      }
-    };
-    const bool ok = (flags & KZGPOT_SUBGROUP_REF) ? in_subgroup_ref<fp2>(load) : in_subgroup_fast_g2(load);
-    if (!ok) st = 5;
-  }
+  if (st == 0 && !g2_in_subgroup(base, flags & KZGPOT_SUBGROUP_REF)) st = 5;
   if (st) store_zero(dst, 12);
   report(i, st, first_bad, status);
 }
@@ -314,77 +240,49 @@ k_g2_check(const uint4* __restrict__ in, uint4* __restrict__ out, uint64_t n, ui
       store_zero(dst, 12);
       return;
     }
-    const uint32_t yb = y1[11] >> 24;
-    const bool fpos = yb & 0x80u;
-    finf = yb & 0x40u;
-    y1[11] &= 0x3fffffffu;
+    bool both;
+    finf = ark_sw_flags(y1[11], both);
     if (words_geq_p(x0) || words_geq_p(x1)) st = 3;
     else if (words_geq_p(y0)) st = 3;
-    else if (fpos && finf) st = 6;
+    else if (both) st = 6;
     else if (words_geq_p(y1)) st = 3;
     if (S != Src::ArkInPlace && st == 0) {
       store_words(dst, x0);
       store_words(dst + 3, x1);
       store_words(dst + 6, y0);
-      words e;
-#pragma unroll
-      for (int k = 0; k < 12; k++) e[k] = y1[k];
-      if (finf) e[11] |= 0x40000000u;
-      store_words(dst + 9, e);
+      store_ark_last(dst + 9, y1, finf);
     }
     if (st == 0 && !finf) {
       fp t;
       words_to_mont(t, x0);
-#pragma unroll
-      for (int k = 0; k < NL; k++) base[k][threadIdx.x] = t.v[k];
+      lds_park(base, t.v);
       words_to_mont(t, x1);
-#pragma unroll
-      for (int k = 0; k < NL; k++) base[NL + k][threadIdx.x] = t.v[k];
+      lds_park(base + NL, t.v);
       words_to_mont(t, y0);
-#pragma unroll
-      for (int k = 0; k < NL; k++) base[2 * NL + k][threadIdx.x] = t.v[k];
+      lds_park(base + 2 * NL, t.v);
       words_to_mont(t, y1);
-#pragma unroll
-      for (int k = 0; k < NL; k++) base[3 * NL + k][threadIdx.x] = t.v[k];
+      lds_park(base + 3 * NL, t.v);
     }
   }
 
   if (st == 0 && !finf) {
-    auto load = [&](fp2& bx, fp2& by) {
-      uint32_t lane = threadIdx.x;
-      asm volatile("" : "+v"(lane));  // opaque index: re-read at every use, never hoisted
-#pragma unroll
-      for (int k = 0; k < NL; k++) {
-        bx.c0.v[k] = base[k][lane];
-        bx.c1.v[k] = base[NL + k][lane];
-        by.c0.v[k] = base[2 * NL + k][lane];
-        by.c1.v[k] = base[3 * NL + k][lane];
-      }
-    };
     bool on_curve;
     {
       fp2 xm, ym, l, r;
-      load(xm, ym);
+      g2_load_base(xm, ym, base);
       f_sqr(l, ym);
       g2_rhs(r, xm);
       fp_sub_red(l.c0, l.c0, r.c0);
       fp_sub_red(l.c1, l.c1, r.c1);
       on_curve = f_is_zero(l);
     }
-    bool ok;
-    if ((flags & KZGPOT_SUBGROUP_REF) || !on_curve)
-      ok = in_subgroup_ref<fp2>(load);
-    else
-      ok = in_subgroup_fast_g2(load);
-    if (!ok) st = 5;
+    if (!g2_in_subgroup(base, (flags & KZGPOT_SUBGROUP_REF) || !on_curve)) st = 5;
   }
   if (st) store_zero(dst, 12);
   report(i, st, first_bad, status);
 }
 
 // ================================================================================ launchers
-static inline unsigned grid_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 hipError_t launch_codec(CodecOp op, const void* d_in, void* d_out, uint64_t n, uint32_t flags,
                         unsigned long long* d_first_bad, uint8_t* d_status, hipStream_t stream) {
   if (n == 0) return hipSuccess;

@@ -52,7 +52,7 @@ def _subgroup_g1(oracle_lib, n, seed):
     return [comp.raw[i * 48:(i + 1) * 48] for i in range(n)]
 
 
-@pytest.mark.parametrize("mode", [0, 4], ids=["fused", "split"])
+@pytest.mark.parametrize("mode", [0, 4, 1], ids=["fused", "split", "unchecked"])
 def test_fuzz_g1_decompress(gpu, oracle_lib, mode):
     rng = random.Random(1234 + mode)
     n = 4000
@@ -63,14 +63,17 @@ def test_fuzz_g1_decompress(gpu, oracle_lib, mode):
         recs.append(rng.choice(valid) if k < 10 else _compressed_fp(rng, _rand_fp(rng), k))
     data = b"".join(recs)
     r = gpu.run_codec("g1_decompress", data, mode, want_status=True)
-    out, st, fb, ret = oracle_run(oracle_lib, "g1_decompress", data, n, threads=8)
+    out, st, fb, ret = oracle_run(oracle_lib, "g1_decompress", data, n, flags=mode, threads=8)
     assert r.status == st
     assert r.out == out
     assert (r.ret, r.first_bad) == (ret, fb)
-    assert st.count(5) > 1000  # thousands of distinct on-curve, off-subgroup points
+    if mode == 1:  # KZGPOT_NO_SUBGROUP_CHECK: phase 1 alone, infinity accepted, no status 5
+        assert all(st.count(s) > 0 for s in (0, 1, 2, 3, 4))
+    else:
+        assert st.count(5) > 1000  # thousands of distinct on-curve, off-subgroup points
 
 
-@pytest.mark.parametrize("mode", [0, 4], ids=["fused", "split"])
+@pytest.mark.parametrize("mode", [0, 4, 1], ids=["fused", "split", "unchecked"])
 def test_fuzz_g2_decompress(gpu, oracle_lib, mode):
     rng = random.Random(4321 + mode)
     n = 1500
@@ -86,11 +89,14 @@ def test_fuzz_g2_decompress(gpu, oracle_lib, mode):
         recs.append(c1 + c0)
     data = b"".join(recs)
     r = gpu.run_codec("g2_decompress", data, mode, want_status=True)
-    out, st, fb, ret = oracle_run(oracle_lib, "g2_decompress", data, n, threads=8)
+    out, st, fb, ret = oracle_run(oracle_lib, "g2_decompress", data, n, flags=mode, threads=8)
     assert r.status == st
     assert r.out == out
     assert (r.ret, r.first_bad) == (ret, fb)
-    assert st.count(5) > 300
+    if mode == 1:
+        assert all(st.count(s) > 0 for s in (0, 1, 2, 3, 4))
+    else:
+        assert st.count(5) > 300
 
 
 def _pairing_uncompressed_g1(ark_rec):

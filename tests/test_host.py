@@ -77,7 +77,7 @@ def test_fake_rccl_exports_what_the_library_binds():
     every RCCL symbol csrc/comm.hip binds (dlsym in rccl())."""
     path = os.path.join(ROOT, "tests", "fake_rccl", "build", "libfake_rccl.so")
     if not os.path.exists(path):
-        subprocess.run(["make", "-C", os.path.dirname(path)], check=True)
+        subprocess.run(["make", "-C", os.path.dirname(os.path.dirname(path))], check=True)  # the Makefile's directory
     src = open(os.path.join(PKG, "csrc", "comm.hip")).read()
     import re
 
