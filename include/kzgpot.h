@@ -199,6 +199,55 @@ int kzgpot_load_phase1_buffer(const uint8_t* file, size_t len, uint32_t exp, uin
                               uint8_t* beta_g2, uint8_t* coeffs_g1, uint8_t* coeffs_g2, uint8_t* alpha_coeffs_g1,
                               uint8_t* beta_coeffs_g1, int* bad_section, int64_t* bad_index);
 
+/* ---------------------------------------------------------------- group FFT, phase1radix2m writer */
+/* The radix-2 FFT in G1 / G2 over the domain of size m = 2^exp generated by
+ * w_m = 7^((r-1)/m) mod r (r the group order): bellman EvaluationDomain<Point<G>>::fft / ifft as
+ * powersoftau's verifier runs them on the first m powers of each section before it writes the
+ * phase1radix2m{exp} file that load_phase1 (src/lib.rs:82-121) reads; also the Lagrange basis of
+ * ark-poly's Radix2EvaluationDomain (same generator 7, same two-adicity 32).
+ *   forward: out[i] = sum_j [w_m^(ij)] in[j];   KZGPOT_FFT_INVERSE: out[i] = [1/m] sum_j [w_m^(-ij)] in[j]
+ * both in natural order. Input: 2^exp ark-uncompressed records (96 B G1 / 192 B G2, what the
+ * codecs above emit; infinity records are legal). A malformed record (coordinate >= p: status 3;
+ * both SWFlags: status 6) is rejected with the loaders' statuses and index, and no output is
+ * written. Points are NOT checked for curve or subgroup membership: the result is defined, and
+ * equals bellman's bytes, only for points of the prime-order subgroup — what a checked decode
+ * guarantees. exp <= 32 (memory permitting). */
+#define KZGPOT_FFT_INVERSE 0x1u     /* monomial -> Lagrange (bellman ifft, incl. the 1/m) */
+#define KZGPOT_FFT_OUT_PAIRING 0x2u /* emit pairing-uncompressed BE records (infinity: 0x40, zeros) instead of ark LE */
+/* w_m as 32 big-endian bytes: bellman's `omega` of EvaluationDomain::from_coeffs (Fr::root_of_unity
+ * squared 32 - exp times). Host only; exp > 32 -> KZGPOT_E_INVALID_ARG. */
+int kzgpot_fr_domain_root(uint32_t exp, uint8_t root_be32[32]);
+/* Bytes of device memory (d_work) the _dev calls below need; 0 for exp > 32. */
+uint64_t kzgpot_group_fft_workspace(int g2, uint32_t exp);
+/* bellman fft / ifft of 2^exp points in HBM, asynchronous on `stream`; d_out may equal d_in.
+ * d_bad_key as for the codecs' _dev calls (reset to all ones, lowered to (index << 8) | status). */
+int kzgpot_g1_fft_dev(const void* d_in, uint32_t exp, void* d_out, uint32_t flags, void* d_work, uint64_t* d_bad_key,
+                      void* stream);
+int kzgpot_g2_fft_dev(const void* d_in, uint32_t exp, void* d_out, uint32_t flags, void* d_work, uint64_t* d_bad_key,
+                      void* stream);
+/* The same on host buffers, synchronous, on the current device. */
+int kzgpot_g1_fft(const uint8_t* in, uint32_t exp, uint8_t* out, uint32_t flags, int64_t* first_bad);
+int kzgpot_g2_fft(const uint8_t* in, uint32_t exp, uint8_t* out, uint32_t flags, int64_t* first_bad);
+
+/* Size of a phase1radix2m{exp} file as powersoftau's verifier writes it: kzgpot_phase1_size(exp)
+ * (what load_phase1 reads) + the 2^exp - 1 H bases (96 B each) that follow. */
+uint64_t kzgpot_phase1radix_size(uint32_t exp);
+/* Replaces the part of powersoftau's verifier (verify_transform_constrained's parameter
+ * preparation) that produces phase1radix2m{exp} from a response transcript of 2^n_log2 powers
+ * (exp <= n_log2). Argument and size checks first (KZGPOT_E_INVALID_ARG / KZGPOT_E_SIZE, no GPU
+ * needed); then the slices tauG1[0, 2m-1), tauG2[0, m), alpha tauG1[0, m), beta tauG1[0, m), betaG2
+ * (m = 2^exp) are decoded with the default checked flags (infinity rejected, subgroup tested —
+ * beta tauG1 and betaG2 included); then, pairing-uncompressed: alpha tauG1[0], beta tauG1[0],
+ * betaG2, ifft(tauG1[0..m)), ifft(tauG2[0..m)), ifft(alpha tauG1[0..m)), ifft(beta tauG1[0..m)),
+ * h[i] = tauG1[m + i] - tauG1[i] for i < m - 1. One GPU (the current device, restored on return).
+ * On a rejected point *bad_section / *bad_index as kzgpot_preprocess. */
+int kzgpot_prepare_phase2_buffer(const uint8_t* transcript, size_t len, uint32_t n_log2, uint32_t exp, uint8_t* out,
+                                 int* bad_section, int64_t* bad_index);
+/* File to file: out_path is written through a temporary "<out_path>.kzgpot-tmp-XXXXXX" renamed over
+ * it on success, so it is either the complete file or untouched. */
+int kzgpot_prepare_phase2(const char* transcript_path, const char* out_path, uint32_t n_log2, uint32_t exp,
+                          int* bad_section, int64_t* bad_index);
+
 /* ---------------------------------------------------------------- BN254 (config 5, next-row §8f 4) */
 /* No reference counterpart: the same path instantiated for ark-bn254 0.2 G1 (cofactor 1).
  * ark compressed (32 B: x LE, SWFlags bit7 PositiveY / bit6 Infinity in byte 31) → ark

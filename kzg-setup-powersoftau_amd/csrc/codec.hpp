@@ -71,4 +71,19 @@ hipError_t launch_bn254(const void* d_in, void* d_out, uint64_t n, unsigned long
 hipError_t launch_codec(CodecOp op, const void* d_in, void* d_out, uint64_t n, uint32_t flags,
                         unsigned long long* d_first_bad, uint8_t* d_status, hipStream_t stream);
 
+// group FFT (fft_kernels.hip). The scalars of one transform, computed on the host (capi.hip) with
+// csrc/fr.hpp: pw[k] = w^(+-2^k) and one in Fr Montgomery form (8 LE words, R = 2^256), minv = 1/m
+// canonical. d_work: fft_workspace_bytes = the twiddle table (fft_twiddle_bytes), then the work buffer.
+struct FftScalars {
+  uint32_t pw[31][8];
+  uint32_t one[8];
+  uint32_t minv[8];
+};
+uint64_t fft_twiddle_bytes(uint32_t exp);
+uint64_t fft_workspace_bytes(bool g2, uint32_t exp);
+hipError_t launch_group_fft(bool g2, const void* d_in, uint32_t exp, void* d_out, bool inverse, bool pairing,
+                            const FftScalars& sc, void* d_work, unsigned long long* d_key, hipStream_t stream);
+// h[i] = tau_g1[m + i] - tau_g1[i], i < m - 1: ark G1 records in, pairing BE records out
+hipError_t launch_h_bases(const void* d_tau_g1, uint64_t m, void* d_out, hipStream_t stream);
+
 }  // namespace kzgpot

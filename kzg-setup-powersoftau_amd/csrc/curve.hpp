@@ -625,4 +625,36 @@ KZG_DEV bool in_subgroup_fast_g2(Load&& load) {
   return jac_eq_affine(q, x, y);
 }
 
+// ---------------------------------------------------------------- inversion, Jacobian -> affine
+// (cold: once per generated point in synth_kernels.hip, once per butterfly in fft_kernels.hip)
+// a^(p-2) = (a^((p-3)/4))^4 a
+KZG_DEV void f_inv(fp& r, const fp& a) {
+  fp t;
+  fp_pow_pm3d4(t, a);
+  fp_sqr(t, t);
+  fp_sqr(t, t);
+  fp_mul(r, t, a);
+}
+KZG_DEV void f_inv(fp2& r, const fp2& a) {  // (a0 - a1 u) / (a0^2 + a1^2); reduced in and out
+  fp n, t;
+  fp_sqr(n, a.c0);
+  fp_sqr(t, a.c1);
+  fp_add(n, n, t);
+  f_inv(n, n);
+  fp_mul(r.c0, a.c0, n);
+  fp_mul(t, a.c1, n);
+  fp_zero(n);
+  fp_sub_red(r.c1, n, t);
+}
+
+template <typename F>
+KZG_DEV void to_affine(F& x, F& y, const jac<F>& p) {
+  F zi, z2;
+  f_inv(zi, p.z);
+  f_sqr(z2, zi);
+  f_mul(x, p.x, z2);
+  f_mul(z2, z2, zi);
+  f_mul(y, p.y, z2);
+}
+
 }  // namespace kzgpot

@@ -1,0 +1,69 @@
+// BLS12-381 scalar field Fr (the group order r) for the group FFT's twiddle factors: 8 x 32-bit
+// little-endian words, Montgomery form with R = 2^256, one CIOS multiply shared by the host
+// (domain root, the powers w^(2^k), m^-1: capi.hip) and the device (k_fft_twiddles builds w^j from
+// those powers, fft_kernels.hip). Nothing here is hot: ~31 multiplies per twiddle against the 254
+// point doublings the twiddle then drives.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bls12_381_consts.hpp"
+
+namespace kzgpot {
+
+struct fr {
+  uint32_t v[8];
+};
+
+// r = 1 (mod 2^32), so -r^-1 mod 2^32 is all ones
+constexpr uint32_t FR_NINV = 0xffffffffu;
+static_assert(FR_R[0] == 1u, "FR_NINV assumes r = 1 mod 2^32");
+
+// a >= r ? a - r : a, for a < 2r given as 8 words plus a carry word
+__host__ __device__ inline void fr_cond_sub(fr& out, const uint32_t (&t)[9]) {
+  uint32_t d[8];
+  int64_t br = 0;
+  for (int i = 0; i < 8; i++) {
+    const int64_t s = (int64_t)t[i] - (int64_t)FR_R[i] + br;
+    d[i] = (uint32_t)s;
+    br = s >> 32;  // 0 or -1
+  }
+  const bool ge = (int64_t)t[8] + br >= 0;
+  for (int i = 0; i < 8; i++) out.v[i] = ge ? d[i] : t[i];
+}
+
+// out = a b R^-1 mod r for a, b < r (CIOS); out < r
+__host__ __device__ inline void fr_mul(fr& out, const fr& a, const fr& b) {
+  uint32_t t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < 8; i++) {
+    uint64_t c = 0;
+    for (int j = 0; j < 8; j++) {
+      const uint64_t s = (uint64_t)a.v[j] * b.v[i] + t[j] + c;
+      t[j] = (uint32_t)s;
+      c = s >> 32;
+    }
+    uint64_t s = (uint64_t)t[8] + c;
+    t[8] = (uint32_t)s;
+    t[9] = (uint32_t)(s >> 32);
+    const uint32_t m = t[0] * FR_NINV;
+    c = ((uint64_t)m * FR_R[0] + t[0]) >> 32;
+    for (int j = 1; j < 8; j++) {
+      s = (uint64_t)m * FR_R[j] + t[j] + c;
+      t[j - 1] = (uint32_t)s;
+      c = s >> 32;
+    }
+    s = (uint64_t)t[8] + c;
+    t[7] = (uint32_t)s;
+    t[8] = t[9] + (uint32_t)(s >> 32);
+  }
+  const uint32_t r9[9] = {t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8]};
+  fr_cond_sub(out, r9);
+}
+
+// Montgomery -> canonical: a * 1
+__host__ __device__ inline void fr_from_mont(fr& out, const fr& a) {
+  fr one = {{1, 0, 0, 0, 0, 0, 0, 0}};
+  fr_mul(out, a, one);
+}
+
+}  // namespace kzgpot

@@ -405,3 +405,76 @@ def load_phase1(exp: int, path: str | None = None) -> Phase1Parameters:
     the default path here too."""
     with open(path or f"../phase1radix2m{exp}", "rb") as f:
         return load_phase1_buffer(f.read(), exp)
+
+
+# ------------------------------------------------------------------ group FFT, phase1radix2m writer
+FFT_INVERSE = 0x1      # monomial -> Lagrange (bellman ifft, incl. the 1/m)
+FFT_OUT_PAIRING = 0x2  # pairing-uncompressed BE records out instead of ark LE
+
+
+def fr_domain_root(exp: int) -> int:
+    """w_m = 7^((r-1) / 2^exp) mod r: bellman's `omega` of the radix-2 domain of size 2^exp."""
+    buf = ctypes.create_string_buffer(32)
+    r = _lib.load().kzgpot_fr_domain_root(exp, buf)
+    if r:
+        raise KzgPotError(r)
+    return int.from_bytes(buf.raw, "big")
+
+
+def group_fft_workspace(g2: bool, exp: int) -> int:
+    return int(_lib.load().kzgpot_group_fft_workspace(int(g2), exp))
+
+
+def phase1radix_size(exp: int) -> int:
+    return int(_lib.load().kzgpot_phase1radix_size(exp))
+
+
+def _group_fft(g2: bool, data, exp: int, inverse: bool, pairing_out: bool) -> CodecResult:
+    rec = 192 if g2 else 96
+    ptr, nbytes, keep = _buf(data)
+    if nbytes != rec << exp:
+        raise ValueError(f"group fft: input length {nbytes} is not 2^{exp} records of {rec} B")
+    out = ctypes.create_string_buffer(nbytes)
+    fb = ctypes.c_int64(-1)
+    flags = (FFT_INVERSE if inverse else 0) | (FFT_OUT_PAIRING if pairing_out else 0)
+    fn = _lib.load().kzgpot_g2_fft if g2 else _lib.load().kzgpot_g1_fft
+    ret = fn(ptr, exp, out, flags, ctypes.byref(fb))
+    del keep
+    if ret <= -100:
+        raise KzgPotError(ret)
+    return CodecResult(out.raw if ret == 0 else b"", ret, fb.value, None)
+
+
+def g1_fft(data, exp: int, inverse: bool = True, pairing_out: bool = False) -> CodecResult:
+    """bellman `EvaluationDomain<Point<G1>>::ifft` (inverse=True: [tau^j]G1 -> [L_i(tau)]G1) or
+    `fft` over 2^exp ark-uncompressed records. A malformed record gives ret = -(status),
+    first_bad = its index and no output. Defined for points of the prime-order subgroup."""
+    return _group_fft(False, data, exp, inverse, pairing_out)
+
+
+def g2_fft(data, exp: int, inverse: bool = True, pairing_out: bool = False) -> CodecResult:
+    return _group_fft(True, data, exp, inverse, pairing_out)
+
+
+def prepare_phase2_buffer(transcript, n_log2: int, exp: int) -> bytes:
+    """A response transcript of 2^n_log2 powers -> the bytes of phase1radix2m{exp} (Lagrange-basis
+    coefficients + H bases, pairing-uncompressed) as powersoftau's verifier writes it."""
+    ptr, nbytes, keep = _buf(transcript)
+    out = ctypes.create_string_buffer(max(1, phase1radix_size(exp)))
+    sec, idx = ctypes.c_int(-1), ctypes.c_int64(-1)
+    r = _lib.load().kzgpot_prepare_phase2_buffer(ptr, nbytes, n_log2, exp, out, ctypes.byref(sec), ctypes.byref(idx))
+    del keep
+    if r:
+        raise KzgPotError(r, idx.value, sec.value)
+    return out.raw[: phase1radix_size(exp)]
+
+
+def prepare_phase2(transcript_path: str, out_path: str | None = None, n_log2: int = TAU_POWERS_LOG2,
+                   exp: int = TAU_POWERS_LOG2) -> None:
+    """File to file; out_path defaults to "phase1radix2m{exp}". Raises KzgPotError with the
+    section and index of a rejected point; out_path is then untouched."""
+    sec, idx = ctypes.c_int(-1), ctypes.c_int64(-1)
+    r = _lib.load().kzgpot_prepare_phase2(transcript_path.encode(), (out_path or f"phase1radix2m{exp}").encode(),
+                                          n_log2, exp, ctypes.byref(sec), ctypes.byref(idx))
+    if r:
+        raise KzgPotError(r, idx.value, sec.value)

@@ -54,6 +54,15 @@ SIGNATURES = {
     "kzgpot_phase1_size": (ctypes.c_uint64, [ctypes.c_uint32]),
     "kzgpot_load_phase1": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32] + [ctypes.c_void_p] * 7 + [intp, i64p]),
     "kzgpot_load_phase1_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32] + [ctypes.c_void_p] * 7 + [intp, i64p]),
+    "kzgpot_fr_domain_root": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_void_p]),
+    "kzgpot_group_fft_workspace": (ctypes.c_uint64, [ctypes.c_int, ctypes.c_uint32]),
+    "kzgpot_g1_fft_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kzgpot_g2_fft_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kzgpot_g1_fft": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, i64p]),
+    "kzgpot_g2_fft": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, i64p]),
+    "kzgpot_phase1radix_size": (ctypes.c_uint64, [ctypes.c_uint32]),
+    "kzgpot_prepare_phase2_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, intp, i64p]),
+    "kzgpot_prepare_phase2": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, intp, i64p]),
     "kzgpot_preprocess_ex": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, intp, i64p]),
     "kzgpot_preprocess_buffer_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, intp, i64p]),
     "kzgpot_blake2b": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

@@ -104,3 +104,35 @@ def codec_dev(op: str, d_in: torch.Tensor, d_out: torch.Tensor, key: torch.Tenso
 
 def read_key(key: torch.Tensor) -> int:
     return int(key.item()) & ((1 << 64) - 1)
+
+
+def group_fft_dev(g2: bool, d_in: torch.Tensor, exp: int, d_out: torch.Tensor, key: torch.Tensor,
+                  inverse: bool = True, pairing_out: bool = False, work: torch.Tensor | None = None) -> torch.Tensor:
+    """Asynchronous group FFT of 2^exp ark records on device tensors (torch's current stream);
+    d_out may be d_in. Allocates the workspace (kzgpot_group_fft_workspace bytes) unless `work` is
+    given; returns it — keep it alive until the stream has run the call."""
+    rec = 192 if g2 else 96
+    if d_in.numel() != rec << exp or d_out.numel() < rec << exp:
+        raise ValueError(f"group fft: bad buffer sizes {d_in.numel()} / {d_out.numel()}")
+    if not (d_in.is_cuda and d_out.is_cuda and key.is_cuda):
+        raise ValueError("group_fft_dev needs device tensors")
+    lib = _lib.load()
+    need = int(lib.kzgpot_group_fft_workspace(int(g2), exp))
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=d_in.device)
+    elif work.numel() < need:
+        raise ValueError(f"group fft: workspace of {work.numel()} B, {need} needed")
+    flags = (1 if inverse else 0) | (2 if pairing_out else 0)
+    fn = lib.kzgpot_g2_fft_dev if g2 else lib.kzgpot_g1_fft_dev
+    rc = fn(d_in.data_ptr(), exp, d_out.data_ptr(), flags, work.data_ptr(), key.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"group fft: launch failed ({rc})")
+    return work
+
+
+def g1_fft_dev(d_in, exp, d_out, key, **kw) -> torch.Tensor:
+    return group_fft_dev(False, d_in, exp, d_out, key, **kw)
+
+
+def g2_fft_dev(d_in, exp, d_out, key, **kw) -> torch.Tensor:
+    return group_fft_dev(True, d_in, exp, d_out, key, **kw)

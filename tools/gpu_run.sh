@@ -30,6 +30,8 @@
 #   campaign_g2   the same on the G2 ops only, with fresh seeds
 #   ab_codec      tools/ab_codec.sh (alternating A/B of two library builds)
 #   census        tools/microbench/bin/fpops_peak + tools/fpops/census.py
+#   lagrange      tools/lagrange_timing.py (group FFT launches at G1 2^16 / 2^20, G2 2^16 / 2^18, and
+#                 prepare_phase2 end to end at 2^21; one process)
 set -o pipefail
 tag=${1:?usage: gpu_run.sh TAG STEP [STEP ...]}
 shift
@@ -77,6 +79,7 @@ for step in "$@"; do
     census) timeout -k 10 120 tools/microbench/bin/fpops_peak > ${o}_fpops_peak.txt &&
             timeout -k 10 300 python3 -u tools/fpops/census.py --peaks ${o}_fpops_peak.txt > ${o}_fp_census.json \
               2> ${o}_fp_census.err ;;
+    lagrange) timeout -k 10 500 python3 -u tools/lagrange_timing.py > ${o}_lagrange.json 2> ${o}_lagrange.err ;;
     *) echo "[gpu_run] unknown step $step" >&2; exit 2 ;;
   esac
   rc=$?
