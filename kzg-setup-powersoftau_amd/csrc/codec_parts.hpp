@@ -113,25 +113,61 @@ KZG_DEV void lds_load(uint32_t (&v)[N], const uint32_t (*rows)[kBlock], uint32_t
 }
 
 // ---------------------------------------------------------------- subgroup tests on a parked point
-// G1: base holds the Montgomery point, x in rows 0.., y in rows NL..; the fast test parks its
-// second ladder's base Q1 = [|u|]P = (X : Y : Z) in qpark (3 NL rows).
-KZG_DEV void g1_load_base(fp& bx, fp& by, const uint32_t (*base)[kBlock]) {
-  const uint32_t lane = lds_lane();
-  lds_load(bx.v, base, lane);
-  lds_load(by.v, base + NL, lane);
+// G1: the ladders run on the 13 x 30 core (curve.hpp), so the point is parked in R30 = 2^390 form
+// with w = 2y: x in rows 0.., w in rows N30.. of base; the fast test parks its second ladder's base
+// Q1 = [|u|]P = (X : W : Z) in qpark (3 N30 rows): 65 rows per lane in all.
+constexpr int kG1BaseRows = 2 * N30, kG1ParkRows = 3 * N30;
+static_assert(kG1ParkRows >= 2 * NL, "the reference-ladder path parks the 14-limb point in qpark");
+
+KZG_DEV void lds_park30(lds_rows rows, const f30& v) {
+#pragma unroll
+  for (int k = 0; k < N30; k++) rows[k][threadIdx.x] = (uint32_t)v.v[k];
 }
-// ref: the reference's double-and-add by r (KZGPOT_SUBGROUP_REF, and every point off the curve)
+KZG_DEV void lds_load30(f30& v, const uint32_t (*rows)[kBlock], uint32_t lane) {
+#pragma unroll
+  for (int k = 0; k < N30; k++) v.v[k] = (int32_t)rows[k][lane];
+}
+// In: the point in R = 2^392 Montgomery form, x normalized with value < 2 p, y canonical or < 2 p
+KZG_DEV void g1_park_base(lds_rows base, const fp& x, const fp& y) {
+  f30 t;
+  f30_from_mont<2>(t, x);
+  lds_park30(base, t);
+  f30_from_mont<1>(t, y);  // w = 2y
+  lds_park30(base + N30, t);
+}
+KZG_DEV void g1_load_base(f30& bx, f30& bw, const uint32_t (*base)[kBlock]) {
+  const uint32_t lane = lds_lane();
+  lds_load30(bx, base, lane);
+  lds_load30(bw, base + N30, lane);
+}
+// ref: the reference's double-and-add by r (KZGPOT_SUBGROUP_REF, and every point off the curve),
+// which stays on 14 x 28 limbs: the point goes back to R = 2^392 form once, parked in qpark
 KZG_DEV bool g1_in_subgroup(const uint32_t (*base)[kBlock], lds_rows qpark, bool ref) {
-  if (ref) return in_subgroup_ref<fp>([&](fp& bx, fp& by) { g1_load_base(bx, by, base); });
-  auto park = [&](const jac<fp>& q) {
-    lds_park(qpark, q.x.v);
-    lds_park(qpark + NL, q.y.v);
-    lds_park(qpark + 2 * NL, q.z.v);
+  if (ref) {
+    {
+      f30 x30, w30;
+      g1_load_base(x30, w30, base);
+      fp t;
+      fp_mont_from_f30<2>(t, x30);
+      lds_park(qpark, t.v);
+      fp_mont_from_f30<1>(t, w30);
+      lds_park(qpark + NL, t.v);
+    }
+    return in_subgroup_ref<fp>([&](fp& bx, fp& by) {
+      const uint32_t lane = lds_lane();
+      lds_load(bx.v, qpark, lane);
+      lds_load(by.v, qpark + NL, lane);
+    });
+  }
+  auto park = [&](const jac<f30>& q) {
+    lds_park30(qpark, q.x);
+    lds_park30(qpark + N30, q.y);
+    lds_park30(qpark + 2 * N30, q.z);
   };
-  auto load_row = [&](int src, fp& bx, fp& by) {  // src 0: P (base), 1: Q1 (qpark); wave-uniform
-    g1_load_base(bx, by, src ? qpark : base);
+  auto load_row = [&](int src, f30& bx, f30& bw) {  // src 0: P (base), 1: Q1 (qpark); wave-uniform
+    g1_load_base(bx, bw, src ? qpark : base);
   };
-  auto load_qz = [&](fp& qz) { lds_load(qz.v, qpark + 2 * NL, lds_lane()); };
+  auto load_qz = [&](f30& qz) { lds_load30(qz, qpark + 2 * N30, lds_lane()); };
   return in_subgroup_fast_g1(load_row, park, load_qz);
 }
 

@@ -65,87 +65,98 @@ KZG_DEV void jac_dbl(jac<fp>& p) {
   fp_negk_nr<BlsFp::KB_2_28>(p.y, d);     // Y3                    < 2^29
 }
 
-// ---------------------------------------------------------------- G1 fast ladders, W = 2Y
+// ---------------------------------------------------------------- G1 fast ladders, W = 2Y, 13 x 30 bits
 // The endomorphism test's ladders (in_subgroup_fast_g1) carry W = 2Y instead of Y: then
 // B' = W^2 = 4B, D = X B' and Z3 = W Z need no 4X / 2Y, and -W3 = 2E (X3 - D) + B'^2 needs no
-// 8 B^2 scaling (fp_mul_addsqr<1>) — per doubling 14 v_lshlrev (4X) and 14 v_lshlrev + 14 adds
-// (8B, 16B) fewer, 14 adds (2 (X3 - D)) more. Every formula is ark's scaled by the exact factor 2
-// on Y, so equal-point and zero tests decide as before; the reference-algorithm ladder
-// (in_subgroup_ref) and the generator keep the Y form. Bounds: tests/field_bounds_model.py
-// jac_dbl_w / jac_madd_w / jac_tpl_affine_w / ladder_invariant_w.
-KZG_DEV void jac_dbl_w(jac<fp>& p) {
-  fp a, b, d, e, t;
-  fp_sqr(a, p.x);              // A = X^2                    N
-  fp_sqr(b, p.y);              // B' = W^2 = 4 Y^2           N
-  fp_mul(d, p.x, b);           // D = X B' = 4 X Y^2         N
-  fp_mul3_nr(e, a);
-  fp_norm(e, e);               // E = 3A                     N
-  fp_mul(p.z, p.y, p.z);       // Z3 = W Z = 2 Y Z           N
-  fp_sqr(a, e);                // F = E^2                    N
-  fp_shl_nr<1>(t, d);          // 2D                        < 2^29
-  fp_subk_nr<BlsFp::KB_8_29>(p.x, a, t);  // X3 = F - 2D           < 2^30 + 2^28
-  fp_mul3_nr(t, d);            // 3D                        < 3 * 2^28
-  fp_subk_nr<BlsFp::KB_8_30>(t, a, t);    // X3 - D = F - 3D       < 2^30 + 2^28
-  fp_shl_nr<1>(t, t);          // 2 (X3 - D)
-  fp_mul_addsqr<1>(d, e, t, b);  // -W3 = E 2 (X3 - D) + B'^2   N
-  fp_negk_nr<BlsFp::KB_2_28>(p.y, d);     // W3                    < 2^29
-}
-
-// 3P from the affine base (x, w = 2y), tpl-2007-bl with Z1 = 1 in W form: YYw = w^2 = 4 YY,
+// 8 B^2 scaling. Every formula is ark's scaled by the exact factor 2 on Y, so equal-point and zero
+// tests decide as before; the reference-algorithm ladder (in_subgroup_ref) and the generator keep
+// the Y form on 14 x 28 limbs.
+// They run on the balanced radix-2^30 core (fp381.hpp f30_*, R30 = 2^390): every reduction scans
+// 169 + 169 (or 91 + 169) products instead of 196 + 196 (105 + 196), and signed digits need no
+// borrowed multiple of p, so a difference is 13 subtractions and values stay below 4.5 p. The price
+// is headroom: a product operand must be balanced, so the lazy sums that feed one (E = 3A,
+// X3 = F - 2D, 2 (X3 - D)) are renormalised by the carry-chain-free f30_norm. B = balanced
+// (|d| <= 2^29 + 4). Digit, top-digit and value bounds of every step, and a bound set closed under
+// a ladder step: tests/f30_ladder_model.py, tests/test_f30_ladder.py.
+// 3P from the affine base (x, w = 2y) is tpl-2007-bl with Z1 = 1 in W form: YYw = w^2 = 4 YY,
 // T = YYw^2 = 16 YYYY, E = 3 x YYw - MM (= 12 x YY - MM), U = (M + E)^2 - MM - EE - T,
-// X3 = 4 (x EE - YYw U), W3 = 2 Y3 = 8 w (U (T - U) - E EE), Z3 = 2E.
-KZG_DEV void jac_tpl_affine_w(jac<fp>& p) {
-  fp x, xx, yy, m, mm, s, e, ee, t, u, n;
-  fp_norm(x, p.x);                              // x (the second ladder's base Q1.X is lazy)
-  fp_sqr(xx, x);                                // XX                     N
-  fp_sqr(yy, p.y);                              // YYw = w^2              N
-  fp_sqr(t, yy);                                // T = YYw^2 = 16 YYYY    N
-  fp_mul3_nr(m, xx);
-  fp_norm(m, m);                                // M = 3 XX               N
-  fp_sqr(mm, m);                                // MM                     N
-  fp_mul(s, x, yy);                             // x YYw                  N
-  fp_mul3_nr(s, s);
-  fp_subk_nr<BlsFp::KB_8_28>(s, s, mm);
-  fp_norm(e, s);                                // E = 3 x YYw - MM       N
-  fp_sqr(ee, e);                                // EE                     N
-  fp_add_nr(s, m, e);
-  fp_sqr(s, s);                                 // S2 = (M + E)^2         N
-  fp_subk_nr<BlsFp::KB_8_28>(s, s, mm);
-  fp_subk_nr<BlsFp::KB_16_28>(s, s, ee);
-  fp_subk_nr<BlsFp::KB_8_28>(s, s, t);
-  fp_norm(u, s);                                // U = S2 - MM - EE - T   N
-  fp_negk_nr<BlsFp::KB_128_28>(n, u);           // -U                    < 2^29
-  fp_mul_sum2(s, x, ee, yy, n);                 // x EE - YYw U           N
-  fp_shl_nr<2>(p.x, s);                         // X3                    < 2^30
-  fp_subk_nr<BlsFp::KB_128_28>(t, t, u);        // T - U                 < 2^30
-  fp_negk_nr<BlsFp::KB_16_28>(n, ee);           // -EE                   < 2^29
-  fp_mul_sum2(s, u, t, e, n);                   // U (T - U) - E EE       N
-  fp_mul(s, p.y, s);
-  fp_shl_nr<3>(s, s);
-  fp_norm(p.y, s);                              // W3 = 8 w (...)         N
-  fp_shl_nr<1>(s, e);
-  fp_norm(p.z, s);                              // Z3 = 2E                N
+// X3 = 4 (x EE - YYw U), W3 = 2 Y3 = 8 w (U (T - U) - E EE), Z3 = 2E. The mixed addition's
+// r = 2 S2 - W1 is ark's r = 2 (S2 - Y1), so X3 = r^2 - J - 2V needs no 4 r'^2, and
+// W3 = 2 Y3 = 2r (V - X3) - 2 W1 J.
+constexpr int F30_ZK = 16;  // the ladders' zero tests see |value| < 16 p (model: < 6 p)
+KZG_DEV void f_one(f30& r) { f30_set(r, ONE30); }
+
+KZG_DEV void jac_dbl_w(jac<f30>& p) {
+  f30 a, b, d, e, t;
+  f30_sqr(a, p.x);             // A = X^2                    B
+  f30_sqr(b, p.y);             // B' = W^2                   B
+  f30_mul(d, p.x, b);          // D = X B'                   B
+  f30_mul3(e, a);
+  f30_norm(e, e);              // E = 3A                     B
+  f30_mul(p.z, p.y, p.z);      // Z3 = W Z                   B
+  f30_sqr(a, e);               // F = E^2                    B
+  f30_dbl(t, d);
+  f30_sub(t, a, t);            // F - 2D                     |d| < 3 * 2^29
+  f30_norm(p.x, t);            // X3                         B
+  f30_sub(t, p.x, d);          // X3 - D                     |d| < 2^30 + 4
+  f30_norm<1>(t, t);           // 2 (X3 - D)                 B
+  f30_mul_addsqr(d, e, t, b);  // -W3 = E 2 (X3 - D) + B'^2  B
+  f30_neg(p.y, d);             // W3                         B
 }
 
-// jac_madd in W form: load(x2, w2) delivers the base with w2 = 2 y2. r = 2 S2 - W1 is ark's
-// r = 2 (S2 - Y1), so X3 = r^2 - J - 2V needs no 4 r'^2, and W3 = 2 Y3 = 2r (V - X3) - 2 W1 J.
+// 3P from the affine base (x, w = 2y), once per ladder
+KZG_DEV void jac_tpl_affine_w(jac<f30>& p) {
+  f30 xx, yy, m, mm, s, e, ee, t, u, n;
+  f30_sqr(xx, p.x);                             // XX
+  f30_sqr(yy, p.y);                             // YYw = w^2
+  f30_sqr(t, yy);                               // T = YYw^2
+  f30_mul3(m, xx);
+  f30_norm(m, m);                               // M = 3 XX               B
+  f30_sqr(mm, m);                               // MM
+  f30_mul(s, p.x, yy);                          // x YYw
+  f30_mul3(s, s);
+  f30_norm(s, s);
+  f30_sub(s, s, mm);
+  f30_norm(e, s);                               // E = 3 x YYw - MM       B
+  f30_sqr(ee, e);                               // EE
+  f30_add(s, m, e);
+  f30_norm(s, s);
+  f30_sqr(s, s);                                // S2 = (M + E)^2
+  f30_sub(s, s, mm);
+  f30_norm(s, s);
+  f30_sub(s, s, ee);
+  f30_norm(s, s);
+  f30_sub(s, s, t);
+  f30_norm(u, s);                               // U = S2 - MM - EE - T   B
+  f30_neg(n, u);
+  f30_mul_sum2(s, p.x, ee, yy, n);              // x EE - YYw U
+  f30_norm<2>(p.x, s);                          // X3 = 4 (...)           B
+  f30_sub(t, t, u);
+  f30_norm(t, t);                               // T - U                  B
+  f30_neg(n, ee);
+  f30_mul_sum2(s, u, t, e, n);                  // U (T - U) - E EE
+  f30_mul(s, p.y, s);
+  f30_norm<3>(p.y, s);                          // W3 = 8 w (...)         B
+  f30_norm<1>(p.z, e);                          // Z3 = 2E                B
+}
+
 template <typename Load>
-KZG_DEV void jac_madd_w(jac<fp>& p, Load&& load) {
-  fp z1z1, h, r, t;
+KZG_DEV void jac_madd_w(jac<f30>& p, Load&& load) {
+  f30 z1z1, h, r, t;
   {
-    fp x2, w2;
+    f30 x2, w2;
     load(x2, w2);
-    fp_sqr(z1z1, p.z);
-    fp_mul(h, x2, z1z1);       // U2
-    f_subk<BlsFp::KB_128_31>(h, h, p.x);
-    fp_norm(h, h);             // H = U2 - X1
-    fp_mul(t, w2, p.z);
-    fp_mul(t, t, z1z1);        // 2 S2
-    f_subk<BlsFp::KB_64_31>(r, t, p.y);
-    fp_norm(r, r);             // r = 2 S2 - W1 = 2 (S2 - Y1)
+    f30_sqr(z1z1, p.z);
+    f30_mul(h, x2, z1z1);      // U2
+    f30_sub(h, h, p.x);
+    f30_norm(h, h);            // H = U2 - X1                B
+    f30_mul(t, w2, p.z);
+    f30_mul(t, t, z1z1);       // 2 S2
+    f30_sub(r, t, p.y);
+    f30_norm(r, r);            // r = 2 S2 - W1              B
   }
-  const bool z1zero = fp_is_zero(p.z);
-  const bool same = !z1zero && fp_is_zero(h) && fp_is_zero(r);
+  const bool z1zero = f30_is_zero<F30_ZK>(p.z);
+  const bool same = !z1zero && f30_is_zero<F30_ZK>(h) && f30_is_zero<F30_ZK>(r);
   if (__builtin_expect(z1zero || same, 0)) {
     if (same) {
       jac_dbl_w(p);
@@ -155,24 +166,25 @@ KZG_DEV void jac_madd_w(jac<fp>& p, Load&& load) {
     }
     return;
   }
-  fp hh, j;
-  fp_sqr(hh, h);               // HH
-  fp_shl_nr<1>(t, p.z);
-  fp_mul(p.z, t, h);           // Z3 = 2 Z1 H
-  fp_shl_nr<2>(hh, hh);
-  fp_norm(hh, hh);             // I = 4 HH
-  fp_mul(j, h, hh);            // J = H I
-  fp_mul(hh, p.x, hh);         // V = X1 I
-  fp_sqr(t, r);                // r^2
-  f_subk<BlsFp::KB_32_28>(t, t, j);
-  fp_shl_nr<1>(h, hh);         // 2V
-  f_subk<BlsFp::KB_64_29>(t, t, h);
-  fp_norm(t, t);               // X3 = r^2 - J - 2V
-  f_subk<BlsFp::KB_128_28>(hh, hh, t);
-  fp_norm(hh, hh);             // V - X3
-  fp_shl_nr<1>(r, r);          // 2r           < 2^29
-  fp_shl_nr<1>(h, p.y);        // 2 W1         < 2^30
-  f_mul_sub(p.y, r, hh, h, j); // W3 = 2r (V - X3) - 2 W1 J
+  f30 hh, j;
+  f30_sqr(hh, h);              // HH
+  f30_dbl(t, p.z);             // 2 Z1                       |d| <= 2^30 + 8
+  f30_mul(p.z, t, h);          // Z3 = 2 Z1 H
+  f30_norm<2>(hh, hh);         // I = 4 HH                   B
+  f30_mul(j, h, hh);           // J = H I
+  f30_mul(hh, p.x, hh);        // V = X1 I
+  f30_sqr(t, r);               // r^2
+  f30_sub(t, t, j);
+  f30_sub(t, t, hh);
+  f30_norm(t, t);              // r^2 - J - V                B
+  f30_sub(t, t, hh);
+  f30_norm(t, t);              // X3 = r^2 - J - 2V          B
+  f30_sub(hh, hh, t);
+  f30_norm(hh, hh);            // V - X3                     B
+  f30_norm<1>(r, r);           // 2r                         B
+  f30_norm<1>(h, p.y);         // 2 W1                       B
+  f30_neg(j, j);
+  f30_mul_sum2(p.y, r, hh, h, j);  // W3 = 2r (V - X3) - 2 W1 J
   p.x = t;
 }
 
@@ -312,7 +324,7 @@ KZG_DEV void jac_madd(jac<fp2>& p, Load&& load) {
 }
 
 // ---------------------------------------------------------------- G2 fast ladder, W = 2Y
-// As the G1 W form (jac_dbl_w above): B' = W^2, D = X B' and Z3 = W Z need no 4X / 2Y, and
+// As the G1 W form (jac_dbl_w(jac<f30>&) above): B' = W^2, D = X B' and Z3 = W Z need no 4X / 2Y, and
 // W3 = (2E)(D - X3) - B'^2 needs no -8 scaling of B^2's factors; the mixed addition's
 // r = 2 S2 - W1 is ark's r. W limbs reach 2^29 (the base's w = 2y), so the constants borrowed
 // against W are KB_*_29. Bounds: tests/field_bounds_model.py jac_dbl_fp2_w / jac_madd_fp2_w /
@@ -492,7 +504,7 @@ KZG_DEV void jac_madd(jac<F>& p, Load&& load) {
 template <typename F, typename Load>
 KZG_DEV void mul_abs_u_affine(jac<F>& acc, Load&& load) {
   static_assert(((BLS_ABS_U >> (BLS_ABS_U_BITS - 2)) & 3) == 3, "|u| starts with the bits 11");
-  if constexpr (__is_same(F, fp)) {  // W = 2Y form: load delivers (x, 2y)
+  if constexpr (__is_same(F, f30)) {  // G1, W = 2Y form: load delivers (x, 2y)
     load(acc.x, acc.y);
     jac_tpl_affine_w(acc);  // [3] B
 #pragma unroll 1
@@ -500,7 +512,8 @@ KZG_DEV void mul_abs_u_affine(jac<F>& acc, Load&& load) {
       jac_dbl_w(acc);
       if ((BLS_ABS_U >> b) & 1) jac_madd_w(acc, load);
     }
-  } else {  // W = 2Y form as well: load delivers (x, y), doubled here
+  } else {  // G2, W = 2Y form as well: load delivers (x, y), doubled here
+    static_assert(__is_same(F, fp2), "the fast ladders run on f30 (G1) and fp2 (G2)");
     auto loadw = [&](fp2& x, fp2& w) {
       load(x, w);
       f2_shl<1>(w, w);
@@ -557,23 +570,35 @@ KZG_DEV bool in_subgroup_ref(Load&& load) {
   return f_is_zero(acc.z);
 }
 
+// The same test on a 13 x 30 ladder state (W form): x, w balanced
+KZG_DEV bool jac_eq_affine(const jac<f30>& p, const f30& x, const f30& w) {
+  f30 z2, t;
+  f30_sqr(z2, p.z);
+  f30_mul(t, x, z2);
+  f30_sub(t, t, p.x);
+  bool ok = f30_is_zero<F30_ZK>(t);
+  f30_mul(z2, z2, p.z);
+  f30_mul(t, w, z2);
+  f30_sub(t, t, p.y);
+  ok = ok && f30_is_zero<F30_ZK>(t);
+  return ok && !f30_is_zero<F30_ZK>(p.z);
+}
+
 // G1: P in G1  <=>  [u^2] P == -phi(P) = (BETA x, -y)   (u^2 = |u|^2)
 // The second [|u|] runs on the isomorphic curve E': y^2 = x^3 + Z^6 b, iota(x, y) = (Z^2 x, Z^3 y),
 // on which Q1 = [|u|] P = (X : Y : Z) is the AFFINE point (X, Y): a = 0 and neither formula reads
 // b, so its 5 additions are mixed additions (8M + 3S) instead of Jacobian ones (12M + 4S), and
 // [|u|] iota(Q1) = (X' : Y' : Z') is (X' : Y' : Z' Z) on E. Q1 = O (Z = 0) still ends in O.
-// load_row(0, x, y) fetches P, park(q1) stores Q1, load_row(1, x, y) / load_qz(z) fetch it back
-// (the kernels park both in LDS). The two ladders are ONE copy of the ladder code, run twice
-// with a wave-uniform source row: each copy is ~25 KB of straight-line doubling code, and two
-// of them plus the square root's loop overflow the 64 KB instruction cache a CU pair shares.
+// Both ladders run on the 13 x 30 core in W form. load_row(0, x, w) fetches P = (x, w = 2y) in R30
+// form, park(q1) stores Q1, load_row(1, x, w) / load_qz(z) fetch it back (the kernels park both in
+// LDS). The two ladders are ONE copy of the ladder code, run twice with a wave-uniform source row:
+// each copy is ~25 KB of straight-line doubling code, and two of them plus the square root's loop
+// overflow the 64 KB instruction cache a CU pair shares.
 template <typename LoadRow, typename Park, typename LoadQZ>
 KZG_DEV bool in_subgroup_fast_g1(LoadRow&& load_row, Park&& park, LoadQZ&& load_qz) {
-  jac<fp> q;
+  jac<f30> q;
   int src = 0;
-  auto load = [&](fp& bx, fp& bw) {  // (x, w = 2y): P's row holds y, Q1's row already holds W
-    load_row(src, bx, bw);
-    if (src == 0) fp_shl_nr<1>(bw, bw);
-  };
+  auto load = [&](f30& bx, f30& bw) { load_row(src, bx, bw); };
 #pragma unroll 1
   for (int pass = 0; pass < 2; pass++) {
     src = __builtin_amdgcn_readfirstlane(pass);
@@ -581,18 +606,16 @@ KZG_DEV bool in_subgroup_fast_g1(LoadRow&& load_row, Park&& park, LoadQZ&& load_
     if (pass == 0) park(q);
   }
   {
-    fp z;
+    f30 z;
     load_qz(z);
-    fp_mul(q.z, q.z, z);
+    f30_mul(q.z, q.z, z);
   }
-  jac<fp>& q2 = q;
-  fp x, y, beta;
-  load_row(0, x, y);
-  fp_set(beta, FP_BETA);
-  fp_mul(x, x, beta);
-  fp_neg(y, y);
-  fp_shl_nr<1>(y, y);  // the ladders carry W = 2Y: compare with 2 (-y)
-  return jac_eq_affine(q2, x, y);
+  f30 x, w, beta;
+  load_row(0, x, w);
+  f30_set(beta, BETA30);
+  f30_mul(x, x, beta);
+  f30_neg(w, w);  // the ladders carry W = 2Y: compare with 2 (-y)
+  return jac_eq_affine(q, x, w);
 }
 
 // psi(x, y) = (conj(x) * (0 + CX1 u), conj(y) * (CY0 + CY1 u))

@@ -42,7 +42,7 @@
 
 namespace kzgpot {
 
-enum class FpOp { Mul, Sqr, MulSum2, MulSum3, MulAddSqr, Mul30, Sqr30, Count };
+enum class FpOp { Mul, Sqr, MulSum2, MulSum3, MulAddSqr, Mul30, Sqr30, Mul30Sum2, Mul30AddSqr, Count };
 
 constexpr uint32_t LMASK = (1u << 28) - 1;  // BLS12-381 limbs (BlsFp::MASK)
 
@@ -530,15 +530,18 @@ KZG_DEV void fp_from_mont(Fe<Tr>& canon, const Fe<Tr>& a) {
 
 // ------------------------------------------------------------------------------- radix-2^30 core
 // BLS12-381's square-root exponentiation (382 squarings + 75 multiplies per call: a third of the
-// G1 codec's instruction stream, 40 % of the G2 codec's) runs on 13 x 30-bit BALANCED limbs:
+// G1 codec's instruction stream, 40 % of the G2 codec's) and the G1 subgroup test's two [|u|]
+// ladders (curve.hpp jac<f30>) run on 13 x 30-bit BALANCED limbs:
 // int32 digits in [-2^29, 2^29), R30 = 2^390, each product one v_mad_i64_i32. Signed digits keep
 // every product below 2^58 in magnitude, so the a*b and m*p column chains (13 products each) still
 // fit one 64-bit accumulator, and a multiply is 169 + 169 mads instead of 196 + 196: 75.8 against
 // 67.9 G multiplies/s, 91 against 83.6 G squarings/s (tools/microbench/mont30s.hip,
 // profiles/r03_mont30_microbench.txt). The price is headroom — an operand digit may not exceed
-// ~2^29.5 — which the ladders' lazy sums need and a pure square-and-multiply chain does not, so only
-// the exponentiation uses it. Bounds: tests/test_fp30.py (worst-case columns for the actual digits
-// of p, and an exact model of every function below against Python integers).
+// ~2^29.5 — which a pure square-and-multiply chain never needs; the ladders renormalise the three
+// lazy sums per doubling that feed a product (f30_norm below). The G2 ladders stay on 14 x 28: their
+// three-product reductions do not fit one int64 here. Bounds: tests/test_fp30.py (worst-case
+// columns for the actual digits of p, an exact model of the exponentiation's functions against
+// Python integers) and tests/f30_ladder_model.py (the ladders' forms and the conversions).
 constexpr int N30 = 13;
 struct f30 {
   int32_t v[N30];
@@ -622,6 +625,148 @@ KZG_DEV void f30_sqr(f30& r, const f30& a) {
   }
   r.v[N - 1] = (int32_t)acc;
 }
+// ---- the forms the G1 subgroup ladders need (curve.hpp, jac<f30>). Operand discipline, proven by
+// tests/f30_ladder_model.py for every call site: a "balanced" value (B) has lower digits
+// |d| <= 2^29 + 4 (f30_norm's slack) and |top digit| <= F30_TOP; f30_mul / f30_sqr also take ONE
+// operand with digits up to 2^30 + 8 (a digit-wise doubled B); the two-product forms below take
+// balanced operands only — their three 13-term chains fill int64 to within 6 %.
+// r = (a b + c d) 2^-390 mod p: both products and the m*p terms in one column scan, one reduction
+KZG_DEV void f30_mul_sum2(f30& r, const f30& a, const f30& b, const f30& c, const f30& d) {
+  KZG_FPOP(FpOp::Mul30Sum2);
+  constexpr int N = N30;
+  int32_t m[N];
+  int64_t acc = 0;
+#pragma unroll
+  for (int i = 0; i < 2 * N - 1; i++) {
+    const int j0 = i < N ? 0 : i - (N - 1);
+    const int j1 = i < N ? i - 1 : N - 1;
+    int64_t accab = i < N ? 0 : (int64_t)1 << 29, acc2 = 0, accp = 0;
+#pragma unroll
+    for (int j = j0; j <= j1; j++) {
+      accab += (int64_t)a.v[j] * b.v[i - j];
+      acc2 += (int64_t)c.v[j] * d.v[i - j];
+      accp += (int64_t)m[j] * P30[i - j];
+    }
+    acc += accab;
+    if (i < N) {
+      acc += (int64_t)a.v[i] * b.v[0];
+      acc2 += (int64_t)c.v[i] * d.v[0];
+      acc += acc2 + accp;
+      m[i] = sext30((uint32_t)acc * PINV30);
+      acc += (int64_t)m[i] * P30[0];
+    } else {
+      acc += acc2 + accp;
+      r.v[i - N] = (int32_t)((uint32_t)acc & ((1u << 30) - 1)) - (1 << 29);
+    }
+    acc >>= 30;
+  }
+  r.v[N - 1] = (int32_t)acc;
+}
+// r = (a b + c^2) 2^-390 mod p, the c^2 half as a squaring (cross products once, as c_j (2 c_k)):
+// the 13-digit form of fp_mul_addsqr<1>, the W-form doubling's -W3 = 2E (X3 - D) + B'^2
+KZG_DEV void f30_mul_addsqr(f30& r, const f30& a, const f30& b, const f30& c) {
+  KZG_FPOP(FpOp::Mul30AddSqr);
+  constexpr int N = N30;
+  int32_t c2[N], m[N];
+#pragma unroll
+  for (int j = 0; j < N; j++) c2[j] = c.v[j] + c.v[j];
+  int64_t acc = 0;
+#pragma unroll
+  for (int i = 0; i < 2 * N - 1; i++) {
+    const int j0 = i < N ? 0 : i - (N - 1);
+    const int j1 = i < N ? i - 1 : N - 1;
+    int64_t accab = i < N ? 0 : (int64_t)1 << 29, acc2 = 0, accp = 0;
+#pragma unroll
+    for (int j = j0; j <= j1; j++) {
+      accab += (int64_t)a.v[j] * b.v[i - j];
+      accp += (int64_t)m[j] * P30[i - j];
+    }
+#pragma unroll
+    for (int j = j0; 2 * j < i; j++) acc2 += (int64_t)c.v[j] * c2[i - j];
+    if ((i & 1) == 0) acc2 += (int64_t)c.v[i / 2] * c.v[i / 2];
+    acc += accab;
+    if (i < N) {
+      acc += (int64_t)a.v[i] * b.v[0];
+      acc += acc2 + accp;
+      m[i] = sext30((uint32_t)acc * PINV30);
+      acc += (int64_t)m[i] * P30[0];
+    } else {
+      acc += acc2 + accp;
+      r.v[i - N] = (int32_t)((uint32_t)acc & ((1u << 30) - 1)) - (1 << 29);
+    }
+    acc >>= 30;
+  }
+  r.v[N - 1] = (int32_t)acc;
+}
+// Digit-wise forms: signed digits need no borrowed multiple of p, so a difference or a negation is
+// 13 VOP2 instructions and adds nothing to the value.
+KZG_DEV void f30_set(f30& r, const int32_t (&c)[N30]) {
+#pragma unroll
+  for (int i = 0; i < N30; i++) r.v[i] = c[i];
+}
+KZG_DEV void f30_add(f30& r, const f30& a, const f30& b) {
+#pragma unroll
+  for (int i = 0; i < N30; i++) r.v[i] = a.v[i] + b.v[i];
+}
+KZG_DEV void f30_sub(f30& r, const f30& a, const f30& b) {
+#pragma unroll
+  for (int i = 0; i < N30; i++) r.v[i] = a.v[i] - b.v[i];
+}
+KZG_DEV void f30_neg(f30& r, const f30& a) {
+#pragma unroll
+  for (int i = 0; i < N30; i++) r.v[i] = -a.v[i];
+}
+KZG_DEV void f30_dbl(f30& r, const f30& a) {
+#pragma unroll
+  for (int i = 0; i < N30; i++) r.v[i] = a.v[i] + a.v[i];
+}
+KZG_DEV void f30_mul3(f30& r, const f30& a) {
+#pragma unroll
+  for (int i = 0; i < N30; i++) r.v[i] = (a.v[i] << 1) + a.v[i];
+}
+// r = 2^S a with balanced digits, for a digit + 2^(29-S) inside int32 (3 x a product's digit just
+// fits S = 0): digit k of 2^S a splits into its balanced low 30 bits (the sign-extended low 30 - S
+// bits of a_k, shifted) and the exact quotient c_k = (a_k + 2^(29-S)) >> (30 - S), which goes to
+// digit k + 1 — every digit at once, no carry chain; |r digit| <= 2^29 + |c|, and |c| <= 4 at
+// every call site (tests/f30_ladder_model.py norm). The top digit takes 2^S a_12 whole.
+template <int S = 0>
+KZG_DEV void f30_norm(f30& r, const f30& a) {
+  static_assert(S >= 0 && S <= 3, "shift");
+  int32_t c = 0;
+#pragma unroll
+  for (int k = 0; k < N30 - 1; k++) {
+    const int32_t lo = __builtin_amdgcn_sbfe(a.v[k], 0, 30 - S);
+    const int32_t cn = (a.v[k] + (1 << (29 - S))) >> (30 - S);
+    r.v[k] = S ? (int32_t)((uint32_t)lo << S) + c : lo + c;
+    c = cn;
+  }
+  r.v[N30 - 1] = (int32_t)((uint32_t)a.v[N30 - 1] << S) + c;
+}
+// a == 0 (mod p) for any digits and |value| <= K p: a = k p forces k = a_0 p^-1 (mod 2^30), and
+// |k| <= K < 2^29 makes that residue's balanced representative the only candidate — a lane whose
+// candidate is outside [-K, K] holds a nonzero value (a nonzero value passes with probability
+// (2K + 1) 2^-30, so the wave almost always leaves through the wave-uniform branch); the others
+// compare a with k p digit by digit through one exact 64-bit carry chain. Exact for every input in
+// the stated range (tests/test_f30_ladder.py).
+template <int K>
+KZG_DEV bool f30_is_zero(const f30& a) {
+  const int32_t k = sext30((uint32_t)a.v[0] * (0u - PINV30));  // PINV30 = -p^-1
+  const bool maybe = (uint32_t)(k + K) <= 2u * K;
+  if (__builtin_amdgcn_ballot_w64(maybe) == 0) return false;
+  if (!maybe) return false;
+  int64_t c = 0;
+  uint32_t diff = 0;
+#pragma unroll
+  for (int i = 0; i < N30; i++) {
+    c += (int64_t)a.v[i] - (int64_t)k * P30[i];
+    if (i < N30 - 1) {
+      diff |= (uint32_t)c & ((1u << 30) - 1);
+      c >>= 30;
+    }
+  }
+  return diff == 0 && c == 0;
+}
+
 // the same integer in balanced 30-bit digits; a: limbs < 2^32 - 16, value < 2^383 (proven in
 // tests/test_fp30.py and test_field_bounds._pow_pm3d4: fp2_sqrt's norm input reaches ~2.02 p)
 KZG_DEV void f30_from_fp(f30& r, const fp& a) {
@@ -641,8 +786,9 @@ KZG_DEV void f30_from_fp(f30& r, const fp& a) {
     }
   }
 }
-// canonical 14 x 28 limbs of a balanced value with |value| < p: + p, unsigned 30-bit digits,
-// 28-bit limbs, one conditional subtraction
+// 14 x 28 limbs of a balanced value z > -p: + p, unsigned 30-bit digits, 28-bit limbs, one
+// conditional subtraction of p. |z| < p (the exponentiation's result) comes out canonical; the
+// parked base point's z in [0, 1.001 p) (fp_mont_from_f30) comes out normalized and below 1.001 p.
 KZG_DEV void fp_from_f30(fp& r, const f30& z) {
   uint32_t u[N30];
   int32_t c = 0;
@@ -664,6 +810,32 @@ KZG_DEV void fp_from_f30(fp& r, const f30& z) {
     r.v[j] = j < NL - 1 ? v & LMASK : v;
   }
   fp_reduce_once(r, r);
+}
+
+// R = 2^392 Montgomery form (normalized, value < 1.001 p: a product, or canonical) -> R30 = 2^390
+// form, balanced, value in [0, 1.001 p), of 2^(2-H) times the element: the representative of x 2^392
+// halved twice is that of x 2^390, so H = 2 keeps the element and H = 1 doubles it (the ladders'
+// w = 2y). 2 x 56 + 80 instructions, once per point. Model: tests/f30_ladder_model.py from_mont.
+template <int H>
+KZG_DEV void f30_from_mont(f30& r, const fp& a) {
+  static_assert(H == 1 || H == 2, "halvings");
+  fp t;
+  fp_half(t, a);
+  if (H == 2) fp_half(t, t);
+  f30_from_fp(r, t);
+}
+// back: an R = 2^392 representative (normalized, value < 1.01 p) of 2^-(2-H) times an R30 value z
+// in [0, 1.001 p): each doubling of a value below 1.004 p is below 2.008 p, and one subtraction
+// of p brings it below 1.008 p (tests/f30_ladder_model.py mont_from_f30)
+template <int H>
+KZG_DEV void fp_mont_from_f30(fp& r, const f30& z) {
+  static_assert(H == 1 || H == 2, "doublings");
+  fp_from_f30(r, z);
+#pragma unroll
+  for (int k = 0; k < H; k++) {
+    fp_add(r, r, r);
+    fp_reduce_once(r, r);
+  }
 }
 
 // The exponentiation schedule as one int32 per step, squarings | table index << 8 (index -1: no

@@ -67,14 +67,15 @@ __global__ void __launch_bounds__(kBlock) k_g1_decompress(const uint4* __restric
 // so nothing but the ladder state is live across the subgroup test,
 // and no record is read back from HBM (48 B in + 96 B out per point, against 48 + 96 + 96 + the
 // x re-read of the split kernels). A rejected point's record is zero-filled (the split path's
-// phase 2 does the same to its poison record). 70 KB of LDS per block (base point + the second
-// ladder's base, as k_g1_check) holds the kernel at 2 waves per SIMD.
+// phase 2 does the same to its poison record). 65 KB of LDS per block (base point + the second
+// ladder's base, as k_g1_check) holds the kernel at 2 waves per SIMD. x's Montgomery form waits in
+// qpark's upper rows until the chosen root is known; the pair is then parked in the ladders' form.
 __global__ void __launch_bounds__(kBlock) k_g1_codec(const uint4* __restrict__ in, uint4* __restrict__ out,
                                                      uint64_t n, uint32_t flags,
                                                      unsigned long long* __restrict__ first_bad,
                                                      uint8_t* __restrict__ status) {
-  __shared__ uint32_t base[2 * NL][kBlock];
-  __shared__ uint32_t qpark[3 * NL][kBlock];
+  __shared__ uint32_t base[kG1BaseRows][kBlock];
+  __shared__ uint32_t qpark[kG1ParkRows][kBlock];
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   wire_head_t h;
@@ -87,7 +88,7 @@ __global__ void __launch_bounds__(kBlock) k_g1_codec(const uint4* __restrict__ i
     lds_park(qpark, w);    // ark x = the canonical x (qpark is free until the ladder)
     fp t;
     words_to_mont(t, w);
-    lds_park(base, t.v);
+    lds_park(qpark + 12, t.v);
     g1_rhs(a, t);
   }
   int st = h.st;
@@ -105,7 +106,9 @@ __global__ void __launch_bounds__(kBlock) k_g1_codec(const uint4* __restrict__ i
       store_words(dst, w);
       store_canon(dst + 3, yc);
       chosen_root_mont(y, keep);
-      lds_park(base + NL, y.v);
+      fp x;
+      lds_load(x.v, qpark + 12, lds_lane());
+      g1_park_base(base, x, y);
     }
   }
   if (st == 0 && !g1_in_subgroup(base, qpark, flags & KZGPOT_SUBGROUP_REF)) st = 5;
@@ -131,19 +134,19 @@ __global__ void __launch_bounds__(kBlock) k_g1_check(const uint4* __restrict__ i
                                                      uint64_t n, uint32_t flags,
                                                      unsigned long long* __restrict__ first_bad,
                                                      uint8_t* __restrict__ status) {
-  // The base point in Montgomery form is parked in LDS (limb-major, so the 64 lanes of a wave hit
-  // 64 consecutive dwords): each of the ~8 reloads in the ladders is 28 LDS reads instead of two
-  // Montgomery conversions, and the point costs no VGPRs between reloads. The fast test's second
-  // ladder base Q1 = [|u|]P = (X : Y : Z) is parked beside it (qpark). 70 KB per 256-lane block:
-  // 2 blocks per CU, the occupancy the VGPR count allows anyway.
-  __shared__ uint32_t base[2 * NL][kBlock];
-  __shared__ uint32_t qpark[3 * NL][kBlock];
+  // The base point in the ladders' form (g1_park_base) is parked in LDS (digit-major, so the 64
+  // lanes of a wave hit 64 consecutive dwords): each of the ~8 reloads in the ladders is 26 LDS
+  // reads instead of two Montgomery conversions, and the point costs no VGPRs between reloads. The
+  // fast test's second ladder base Q1 = [|u|]P = (X : W : Z) is parked beside it (qpark). 65 KB per
+  // 256-lane block: 2 blocks per CU, the occupancy the VGPR count allows anyway.
+  __shared__ uint32_t base[kG1BaseRows][kBlock];
+  __shared__ uint32_t qpark[kG1ParkRows][kBlock];
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   const uint4* rec = (src_in_place(S) ? (const uint4*)out : in) + i * 6;
   uint4* dst = out + i * 6;
   int st = 0;
-  bool finf;
+  bool finf, on_curve = true;
   {
     // The record is read ONCE: a transcode record that passes the flag and field checks is
     // emitted right away (as k_g1_codec emits before its subgroup test) and zero-filled if the
@@ -167,24 +170,19 @@ __global__ void __launch_bounds__(kBlock) k_g1_check(const uint4* __restrict__ i
       fp bx, by;
       words_to_mont(bx, x);
       words_to_mont(by, y);
-      lds_park(base, bx.v);
-      lds_park(base + NL, by.v);
+      g1_park_base(base, bx, by);
+      // Phase 1 emits only points with y^2 = x^3 + 4 (it rejects non-residues), so an in-place
+      // record is on the curve; a transcode input may not be (the reference never checks).
+      if (S != Src::ArkInPlace) {
+        fp l, r;
+        fp_sqr(l, by);
+        g1_rhs(r, bx);
+        on_curve = fp_eq(l, r);
+      }
     }
   }
 
-  if (st == 0 && !finf) {
-    // Phase 1 emits only points with y^2 = x^3 + 4 (it rejects non-residues), so an in-place
-    // record is on the curve; a transcode input may not be (the reference never checks).
-    bool on_curve = true;
-    if (S != Src::ArkInPlace) {
-      fp xm, ym, l, r;
-      g1_load_base(xm, ym, base);
-      fp_sqr(l, ym);
-      g1_rhs(r, xm);
-      on_curve = fp_eq(l, r);
-    }
-    if (!g1_in_subgroup(base, qpark, (flags & KZGPOT_SUBGROUP_REF) || !on_curve)) st = 5;
-  }
+  if (st == 0 && !finf && !g1_in_subgroup(base, qpark, (flags & KZGPOT_SUBGROUP_REF) || !on_curve)) st = 5;
   if (st) store_zero(dst, 6);
   report(i, st, first_bad, status);
 }

@@ -10,7 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-__device__ unsigned long long g_fpops[8];
+__device__ unsigned long long g_fpops[16];
 #define KZG_FPOP(kind) atomicAdd(&g_fpops[(int)(kind)], 1ull)
 
 #include "../../kzg-setup-powersoftau_amd/csrc/bn254_kernels.hip"
@@ -25,16 +25,16 @@ __device__ unsigned long long g_fpops[8];
 extern "C" int fp_census_run(int op, const void* d_in, uint64_t n, void* d_out, uint32_t flags, uint8_t* d_status,
                              unsigned long long* counts, unsigned long long* first_bad) {
   constexpr int K = (int)kzgpot::FpOp::Count;
-  static_assert(K <= 8, "census slots");
+  static_assert(K <= 16, "census slots");
   if (op < 0 || op > (int)kzgpot::CodecOp::Bn254G1Decompress) return (int)hipErrorInvalidValue;
-  unsigned long long zero[8] = {0}, *d_key = nullptr;
+  unsigned long long zero[16] = {0}, *d_key = nullptr;
   hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_fpops), zero, sizeof zero);
   if (e == hipSuccess) e = hipMalloc(&d_key, sizeof *d_key);
   if (e == hipSuccess) e = hipMemset(d_key, 0xff, sizeof *d_key);
   if (e == hipSuccess)
     e = kzgpot::launch_codec((kzgpot::CodecOp)op, d_in, d_out, n, flags, d_key, d_status, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  unsigned long long got[8];
+  unsigned long long got[16];
   if (e == hipSuccess) e = hipMemcpyFromSymbol(got, HIP_SYMBOL(g_fpops), sizeof got);
   if (e == hipSuccess) e = hipMemcpy(first_bad, d_key, sizeof *d_key, hipMemcpyDeviceToHost);
   if (e == hipSuccess)

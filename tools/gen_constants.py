@@ -279,6 +279,8 @@ def main():
         arr_s32("P30", balanced30(P), "p, balanced 30-bit digits"),
         f"static constexpr uint32_t PINV30 = 0x{(-pow(P, -1, 1 << 30)) % (1 << 30):08x}u;  // -p^-1 mod 2^30",
         arr_s32("POW30_OUT", balanced30(pow30_out), "2^392 4^-e mod p, e = (p-3)/4: R30-domain (4a)^e -> R = 2^392 a^e"),
+        arr_s32("ONE30", balanced30((1 << 390) % P), "1 in R30 form (the G1 ladders on the radix-2^30 core, curve.hpp)"),
+        arr_s32("BETA30", balanced30(beta * (1 << 390) % P), "BETA in R30 form"),
         f"static constexpr uint64_t BLS_ABS_U = 0x{absu:016x}ull;  // |u|, u < 0",
         "static constexpr int BLS_ABS_U_BITS = %d;" % absu.bit_length(),
         arr("FR_R", words32(R, 8), "group order r (ref-mode double-and-add)"),

@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -29,7 +30,7 @@
 enum Op {
   MAD64, MULLO, MULHI, ADD, SUB, ADDCO, ADDC, AND, XOR, LSHR, LSHL, LSHR64, LSHLADD64, LSHLADD, ADD3,
   ANDOR, OR3, CNDMASK, MOV, BFE, ALIGNBIT, MUL24, MULHI24, MAD24, FMA64, MIX_MAD_AND, MIX_MAD3_ADD,
-  MIX_MAD_LSHR64, MIX_MAD_MULLO, NOPS
+  MIX_MAD_LSHR64, MIX_MAD_MULLO, MADI64, BFEI, ASHR, ASHR64, NOPS
 };
 static const char* kName[NOPS] = {
     "v_mad_u64_u32", "v_mul_lo_u32", "v_mul_hi_u32", "v_add_u32", "v_sub_u32", "v_add_co_u32",
@@ -37,7 +38,10 @@ static const char* kName[NOPS] = {
     "v_lshl_add_u64", "v_lshl_add_u32", "v_add3_u32", "v_and_or_b32", "v_or3_b32", "v_cndmask_b32",
     "v_mov_b32", "v_bfe_u32", "v_alignbit_b32", "v_mul_u32_u24", "v_mul_hi_u32_u24", "v_mad_u32_u24",
     "v_fma_f64", "mix 1 mad64 : 1 and", "mix 3 mad64 : 1 add", "mix 1 mad64 : 1 lshr64",
-    "mix 1 mad64 : 1 mul_lo"};
+    "mix 1 mad64 : 1 mul_lo",
+    // the radix-2^30 core's opcodes (fp381.hpp f30_*): the signed mad, the digit extraction and
+    // the arithmetic shifts of the carries
+    "v_mad_i64_i32", "v_bfe_i32", "v_ashrrev_i32", "v_ashrrev_i64"};
 
 template <int OP>
 __device__ __forceinline__ void step(uint32_t& x, uint64_t& a, double& f, uint32_t y, uint64_t y64, double g,
@@ -108,9 +112,18 @@ __device__ __forceinline__ void step(uint32_t& x, uint64_t& a, double& f, uint32
   } else if constexpr (OP == MIX_MAD_MULLO) {
     step<MAD64>(x, a, f, y, y64, g, smask);
     step<MULLO>(x, a, f, y, y64, g, smask);
+  } else if constexpr (OP == MADI64) {
+    uint64_t cc;
+    asm volatile("v_mad_i64_i32 %0, %1, %2, %3, %0" : "+v"(a), "=s"(cc) : "v"(x), "v"(y));
+  } else if constexpr (OP == BFEI) {
+    asm volatile("v_bfe_i32 %0, %0, 0, 30" : "+v"(x));
+  } else if constexpr (OP == ASHR) {
+    asm volatile("v_ashrrev_i32 %0, 5, %0" : "+v"(x));
+  } else if constexpr (OP == ASHR64) {
+    asm volatile("v_ashrrev_i64 %0, 30, %0" : "+v"(a));
   }
 }
-constexpr int ops_per_step(int op) { return op == MIX_MAD3_ADD ? 4 : (op >= MIX_MAD_AND ? 2 : 1); }
+constexpr int ops_per_step(int op) { return op == MIX_MAD3_ADD ? 4 : (op >= MIX_MAD_AND && op <= MIX_MAD_MULLO ? 2 : 1); }
 
 // CH independent chains, each advanced UNROLL times per loop iteration.
 template <int OP, int CH>
@@ -194,7 +207,8 @@ Res run(int op, int ch, int W, int cus, uint64_t* out, uint64_t* clk, std::vecto
   return r;
 }
 
-int main() {
+// valu_issue [first-op-name]: with a name, only that opcode and the ones after it in kName
+int main(int argc, char** argv) {
   hipDeviceProp_t prop;
   CHECK(hipGetDeviceProperties(&prop, 0));
   const int cus = prop.multiProcessorCount;
@@ -211,10 +225,13 @@ int main() {
   std::vector<uint64_t> h((size_t)cus * maxW * 4 * 4);
   const int Ws[6] = {1, 2, 3, 4, 6, 8};
   const int chs[4] = {1, 2, 4, 8};
-  for (int op = 0; op < NOPS; op++) {
+  int first = 0;
+  for (int op = 0; argc > 1 && op < NOPS; op++)
+    if (!strcmp(argv[1], kName[op])) first = op;
+  for (int op = first; op < NOPS; op++) {
     printf("\n%-22s        W=1         W=2         W=3         W=4         W=6         W=8\n", kName[op]);
     for (int ci = 0; ci < 4; ci++) {
-      const bool all_chains = op == MAD64 || op == ADD || op == MIX_MAD_AND || op == MIX_MAD3_ADD;
+      const bool all_chains = op == MAD64 || op == MADI64 || op == ADD || op == MIX_MAD_AND || op == MIX_MAD3_ADD;
       if (!all_chains && chs[ci] != 1 && chs[ci] != 8) continue;
       printf("  chains=%d         ", chs[ci]);
       double mhz = 0;

@@ -1,14 +1,15 @@
 """Cycle-weighted integer-VALU roof of the codec kernels.
 
     python tools/valu_mix.py [--lib kzg-setup-powersoftau_amd/build/libkzgpot.so]
-                             [--costs profiles/r02_valu_issue_microbench.txt]
+                             [--costs profiles/r02_valu_issue_microbench.txt profiles/r08_valu_issue_i64.txt]
                              [--out profiles/r02_valu_mix.json]
 
 For every kernel in the library's gfx950 code objects:
   * the opcode histogram of its machine code (llvm-objdump), VALU opcodes only;
   * each opcode's issue cost in SIMD cycles per wave64 instruction, measured by
     tools/microbench/valu_issue.hip (the "chains=1" row at 4 waves per SIMD, chip-wide: enough
-    waves that latency is hidden and the SIMD's issue rate is the limit); opcodes the
+    waves that latency is hidden and the SIMD's issue rate is the limit; a later file adds the
+    radix-2^30 core's opcodes, v_mad_i64_i32 / v_bfe_i32 / v_ashrrev_*); opcodes the
     microbenchmark does not cover take the cost of their encoding class (VOP2 2-operand 32-bit
     ALU = v_add_u32's, everything else = v_mul_lo_u32's);
   * the mix-weighted average cost = the SIMD cycles one VALU instruction of this kernel needs
@@ -128,13 +129,17 @@ def waves_per_simd(md, block=256):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=os.path.join(ROOT, "kzg-setup-powersoftau_amd", "build", "libkzgpot.so"))
-    ap.add_argument("--costs", default=os.path.join(ROOT, "profiles", "r02_valu_issue_microbench.txt"))
+    ap.add_argument("--costs", nargs="+", default=[os.path.join(ROOT, "profiles", "r02_valu_issue_microbench.txt"),
+                                                   os.path.join(ROOT, "profiles", "r08_valu_issue_i64.txt")])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r02_valu_mix.json"))
     a = ap.parse_args()
-    costs = parse_costs(a.costs)
+    costs = {}
+    for path in a.costs:
+        if os.path.exists(path):
+            costs.update(parse_costs(path))
     res = {"source": "tools/valu_mix.py: static opcode histogram of each kernel's gfx950 code x per-opcode issue "
                      "cost (SIMD cycles per wave64 instruction, chains=1 / 4 waves per SIMD, chip-wide) from "
-                     + os.path.relpath(a.costs, ROOT),
+                     + ", ".join(os.path.relpath(c, ROOT) for c in a.costs),
            "costs": costs, "kernels": {}}
     with tempfile.TemporaryDirectory() as tmp:
         for co in extract(a.lib, tmp):
