@@ -1,4 +1,4 @@
-// Internal C++ interface between the C ABI (capi.hip) and the kernels (codec_kernels.hip,
+// Internal C++ interface between the C ABI (capi.hip, preprocess.hip, phase2.hip) and the kernels (codec_kernels.hip,
 // g1_kernels.hip; the device functions those two share are in codec_parts.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -71,7 +71,7 @@ hipError_t launch_bn254(const void* d_in, void* d_out, uint64_t n, unsigned long
 hipError_t launch_codec(CodecOp op, const void* d_in, void* d_out, uint64_t n, uint32_t flags,
                         unsigned long long* d_first_bad, uint8_t* d_status, hipStream_t stream);
 
-// group FFT (fft_kernels.hip). The scalars of one transform, computed on the host (capi.hip) with
+// group FFT (fft_kernels.hip). The scalars of one transform, computed on the host (phase2.hip) with
 // csrc/fr.hpp: pw[k] = w^(+-2^k) and one in Fr Montgomery form (8 LE words, R = 2^256), minv = 1/m
 // canonical. d_work: fft_workspace_bytes = the twiddle table (fft_twiddle_bytes), then the work buffer.
 struct FftScalars {

@@ -1,6 +1,6 @@
 // BLS12-381 scalar field Fr (the group order r) for the group FFT's twiddle factors: 8 x 32-bit
 // little-endian words, Montgomery form with R = 2^256, one CIOS multiply shared by the host
-// (domain root, the powers w^(2^k), m^-1: capi.hip) and the device (k_fft_twiddles builds w^j from
+// (domain root, the powers w^(2^k), m^-1: phase2.hip) and the device (k_fft_twiddles builds w^j from
 // those powers, fft_kernels.hip). Nothing here is hot: ~31 multiplies per twiddle against the 254
 // point doublings the twiddle then drives.
 #pragma once

@@ -1,0 +1,246 @@
+// C ABI (include/kzgpot.h): the G1 / G2 group FFT and the phase1radix2m (Lagrange-basis) writer,
+// with the host-side Fr arithmetic (csrc/fr.hpp) that computes each transform's scalars.
+#include <string.h>
+
+#include "accumulator.hpp"
+#include "codec.hpp"
+#include "device_rt.hpp"
+#include "fr.hpp"
+#include "host_rt.hpp"
+
+using namespace kzgpot;
+
+namespace {
+
+// Fr on the host (csrc/fr.hpp's multiply): R = 2^256 mod r and R^2 by repeated doubling
+struct FrHost {
+  fr one, r2;
+  FrHost() {
+    fr x = {{1, 0, 0, 0, 0, 0, 0, 0}};
+    for (int i = 0; i < 512; i++) {  // x = 2^(i + 1) mod r
+      uint32_t t[9];
+      uint32_t c = 0;
+      for (int k = 0; k < 8; k++) {
+        t[k] = (x.v[k] << 1) | c;
+        c = x.v[k] >> 31;
+      }
+      t[8] = c;
+      fr_cond_sub(x, t);
+      if (i == 255) one = x;
+    }
+    r2 = x;
+  }
+  fr to_mont(uint64_t a) const {
+    fr x = {{(uint32_t)a, (uint32_t)(a >> 32), 0, 0, 0, 0, 0, 0}}, y;
+    fr_mul(y, x, r2);
+    return y;
+  }
+  fr pow(const fr& base, const uint32_t (&e)[8]) const {  // base in Montgomery form, e any 256-bit exponent
+    fr acc = one;
+    for (int b = 255; b >= 0; b--) {
+      fr_mul(acc, acc, acc);
+      if ((e[b >> 5] >> (b & 31)) & 1) fr_mul(acc, acc, base);
+    }
+    return acc;
+  }
+};
+const FrHost& fr_host() {
+  static const FrHost h;
+  return h;
+}
+
+// w_m = 7^((r - 1) / 2^exp) in Montgomery form: bellman's omega for the domain of size 2^exp
+// (its root_of_unity = 7^((r-1)/2^32) squared 32 - exp times), and ark-poly's Radix2EvaluationDomain's
+fr domain_root_mont(uint32_t exp) {
+  uint32_t rm1[9], e[8];
+  for (int k = 0; k < 8; k++) rm1[k] = FR_R[k];
+  rm1[0] -= 1;  // r is odd
+  rm1[8] = 0;
+  for (int k = 0; k < 8; k++) e[k] = (uint32_t)((((uint64_t)rm1[k + 1] << 32) | rm1[k]) >> exp);  // exp <= 32
+  const FrHost& h = fr_host();
+  return h.pow(h.to_mont(7), e);
+}
+
+// The scalars of one transform of size m = 2^exp: the powers w^(+-2^k) (the inverse uses
+// w^-1 = w^(m-1)) and 1/m = m^(r-2)
+void fft_scalars(uint32_t exp, bool inverse, FftScalars& sc) {
+  const FrHost& h = fr_host();
+  const uint64_t m = (uint64_t)1 << exp;
+  fr w = domain_root_mont(exp);
+  if (inverse) {
+    const uint32_t e[8] = {(uint32_t)(m - 1), 0, 0, 0, 0, 0, 0, 0};  // m - 1 < 2^32
+    w = h.pow(w, e);
+  }
+  for (int k = 0; k < 31; k++) {
+    memcpy(sc.pw[k], w.v, sizeof w.v);
+    fr_mul(w, w, w);
+  }
+  memcpy(sc.one, h.one.v, sizeof sc.one);
+  uint32_t rm2[8];
+  int64_t br = -2;
+  for (int k = 0; k < 8; k++) {
+    const int64_t s = (int64_t)FR_R[k] + br;
+    rm2[k] = (uint32_t)s;
+    br = s >> 32;
+  }
+  fr minv;
+  fr_from_mont(minv, h.pow(h.to_mont(m), rm2));
+  memcpy(sc.minv, minv.v, sizeof sc.minv);
+}
+
+constexpr uint32_t kFftFlags = KZGPOT_FFT_INVERSE | KZGPOT_FFT_OUT_PAIRING;
+
+// host_key (optional): receives the bad key once the transform is done
+int fft_dev(bool g2, const void* d_in, uint32_t exp, void* d_out, uint32_t flags, void* d_work, uint64_t* d_bad_key,
+            void* stream, uint64_t* host_key = nullptr) {
+  if (exp > 32 || !d_in || !d_out || !d_work || !d_bad_key || (flags & ~kFftFlags)) return KZGPOT_E_INVALID_ARG;
+  FftScalars sc;
+  fft_scalars(exp, flags & KZGPOT_FFT_INVERSE, sc);
+  const hipStream_t s = (hipStream_t)stream;
+  return launch_with_key(d_bad_key, s, [&](unsigned long long* key) {
+    return launch_group_fft(g2, d_in, exp, d_out, flags & KZGPOT_FFT_INVERSE, flags & KZGPOT_FFT_OUT_PAIRING, sc,
+                            d_work, key, s);
+  }, host_key);
+}
+
+int fft_host(bool g2, const uint8_t* in, uint32_t exp, uint8_t* out, uint32_t flags, int64_t* first_bad) {
+  if (first_bad) *first_bad = -1;
+  if (exp > 32 || !in || !out || (flags & ~kFftFlags)) return KZGPOT_E_INVALID_ARG;
+  if (device_count() <= 0) return KZGPOT_E_DEVICE;
+  DeviceGuard guard;
+  const uint64_t bytes = ((uint64_t)1 << exp) * (g2 ? 192 : 96);
+  DevBuf io, work, key;
+  if (io.alloc(bytes) || work.alloc(fft_workspace_bytes(g2, exp)) || key.alloc(sizeof(uint64_t))) return KZGPOT_E_DEVICE;
+  HIP_TRY(hipMemcpy(io.p, in, bytes, hipMemcpyHostToDevice));
+  uint64_t k;
+  if (const int r = fft_dev(g2, io.p, exp, io.p, flags, work.p, (uint64_t*)key.p, nullptr, &k)) return r;
+  if (k != kNoBad) return decode_key(k, first_bad);  // rejected: nothing is written
+  HIP_TRY(hipMemcpy(out, io.p, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// a finite ark-uncompressed record -> pairing uncompressed (A6): every 48-B coordinate byte-reversed,
+// G2's c0 / c1 swapped
+void ark_to_pairing(uint8_t* dst, const uint8_t* ark, bool g2) {
+  const int nc = g2 ? 4 : 2;
+  for (int c = 0; c < nc; c++) {
+    const uint8_t* src = ark + 48 * (g2 ? (c ^ 1) : c);
+    for (int b = 0; b < 48; b++) dst[48 * c + b] = src[47 - b];
+  }
+}
+
+// powersoftau's verifier, the part that writes phase1radix2m{exp}: checked decode of the five
+// slices, then alpha, beta_g1, beta_g2, the four inverse FFTs and the H bases, pairing-uncompressed
+int prepare_phase2_run(const uint8_t* tr, uint32_t n_log2, uint32_t exp, uint8_t* out, int* bad_section,
+                       int64_t* bad_index) {
+  if (device_count() <= 0) return KZGPOT_E_DEVICE;
+  DeviceGuard guard;
+  const uint64_t m = 1ull << exp;
+  const Accumulator in_file(1ull << n_log2), use(m);  // the first `use` points of each section are read
+  hipStream_t s = nullptr;
+  DevBuf comp, dec[Accumulator::kSections], tmp, work, key;
+  if (comp.alloc(use.cnt[0] * 96) || tmp.alloc(m * 192) || work.alloc(fft_workspace_bytes(true, exp)) ||
+      key.alloc(sizeof(uint64_t)))
+    return KZGPOT_E_DEVICE;
+  for (int sec = 0; sec < Accumulator::kSections; sec++) {
+    const CodecOp op = Accumulator::g2(sec) ? CodecOp::G2Decompress : CodecOp::G1Decompress;
+    const uint64_t rin = in_record(op), rout = out_record(op), cnt = use.cnt[sec];
+    if (dec[sec].alloc(cnt * rout)) return KZGPOT_E_DEVICE;
+    HIP_TRY(hipMemcpy(comp.p, tr + in_file.offset(sec), cnt * rin, hipMemcpyHostToDevice));
+    uint64_t k;
+    const int r = launch_with_key((uint64_t*)key.p, s, [&](unsigned long long* d_key) {
+      return launch_codec(op, comp.p, dec[sec].p, cnt, 0, d_key, nullptr, s);
+    }, &k);
+    if (r) return r;
+    if (k != kNoBad) {
+      if (bad_section) *bad_section = sec;
+      return decode_key(k, bad_index);
+    }
+  }
+  uint8_t head[192];
+  uint8_t* o = out;
+  for (int sec = 2; sec < 5; sec++) {  // alpha = alpha tau^0 G1, beta_g1, beta_g2
+    const size_t rec = Accumulator::g2(sec) ? 192 : 96;
+    HIP_TRY(hipMemcpy(head, dec[sec].p, rec, hipMemcpyDeviceToHost));
+    ark_to_pairing(o, head, Accumulator::g2(sec));
+    o += rec;
+  }
+  uint8_t* const h_out = o + m * (3 * 96 + 192);
+  HIP_TRY(launch_h_bases(dec[0].p, m, tmp.p, s));
+  HIP_TRY(hipMemcpy(h_out, tmp.p, (m - 1) * 96, hipMemcpyDeviceToHost));
+  for (int sec = 0; sec < 4; sec++) {  // coeffs_g1, coeffs_g2, alpha_coeffs_g1, beta_coeffs_g1
+    const size_t bytes = m * (Accumulator::g2(sec) ? 192 : 96);
+    uint64_t k;
+    if (const int r = fft_dev(Accumulator::g2(sec), dec[sec].p, exp, tmp.p, kFftFlags, work.p, (uint64_t*)key.p, s, &k))
+      return r;
+    if (k != kNoBad) return KZGPOT_E_DEVICE;  // the records are the codec's own output
+    HIP_TRY(hipMemcpy(o, tmp.p, bytes, hipMemcpyDeviceToHost));
+    o += bytes;
+  }
+  return 0;
+}
+
+int prepare_phase2_args(const void* a, const void* b, uint32_t n_log2, uint32_t exp, int* bad_section,
+                        int64_t* bad_index) {
+  reset_bad(bad_section, bad_index);
+  if (!a || !b || n_log2 < 1 || n_log2 > 30 || exp > n_log2) return KZGPOT_E_INVALID_ARG;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* host only */
+int kzgpot_fr_domain_root(uint32_t exp, uint8_t root_be32[32]) {
+  if (exp > 32 || !root_be32) return KZGPOT_E_INVALID_ARG;
+  return api_guard([&] {
+    fr w;
+    fr_from_mont(w, domain_root_mont(exp));
+    for (int k = 0; k < 8; k++)
+      for (int b = 0; b < 4; b++) root_be32[31 - 4 * k - b] = (uint8_t)(w.v[k] >> (8 * b));
+    return 0;
+  });
+}
+uint64_t kzgpot_group_fft_workspace(int g2, uint32_t exp) { return exp > 32 ? 0 : fft_workspace_bytes(g2 != 0, exp); }
+int kzgpot_g1_fft_dev(const void* d_in, uint32_t exp, void* d_out, uint32_t flags, void* d_work, uint64_t* d_bad_key,
+                      void* stream) {
+  return api_guard([&] { return fft_dev(false, d_in, exp, d_out, flags, d_work, d_bad_key, stream); });
+}
+int kzgpot_g2_fft_dev(const void* d_in, uint32_t exp, void* d_out, uint32_t flags, void* d_work, uint64_t* d_bad_key,
+                      void* stream) {
+  return api_guard([&] { return fft_dev(true, d_in, exp, d_out, flags, d_work, d_bad_key, stream); });
+}
+int kzgpot_g1_fft(const uint8_t* in, uint32_t exp, uint8_t* out, uint32_t flags, int64_t* first_bad) {
+  return api_guard([&] { return fft_host(false, in, exp, out, flags, first_bad); });
+}
+int kzgpot_g2_fft(const uint8_t* in, uint32_t exp, uint8_t* out, uint32_t flags, int64_t* first_bad) {
+  return api_guard([&] { return fft_host(true, in, exp, out, flags, first_bad); });
+}
+
+uint64_t kzgpot_phase1radix_size(uint32_t exp) {
+  if (exp > 30) return 0;
+  return kzgpot_phase1_size(exp) + ((1ull << exp) - 1) * 96;
+}
+int kzgpot_prepare_phase2_buffer(const uint8_t* transcript, size_t len, uint32_t n_log2, uint32_t exp, uint8_t* out,
+                                 int* bad_section, int64_t* bad_index) {
+  if (const int r = prepare_phase2_args(transcript, out, n_log2, exp, bad_section, bad_index)) return r;
+  if (len != kzgpot_contribution_size(n_log2)) return KZGPOT_E_SIZE;
+  return api_guard([&] { return prepare_phase2_run(transcript, n_log2, exp, out, bad_section, bad_index); });
+}
+int kzgpot_prepare_phase2(const char* transcript_path, const char* out_path, uint32_t n_log2, uint32_t exp,
+                          int* bad_section, int64_t* bad_index) {
+  if (const int r = prepare_phase2_args(transcript_path, out_path, n_log2, exp, bad_section, bad_index)) return r;
+  return api_guard([&]() -> int {
+    std::vector<uint8_t> tr;
+    if (const int r = read_file(transcript_path, tr, kzgpot_contribution_size(n_log2))) return r;
+    std::vector<uint8_t> out(kzgpot_phase1radix_size(exp));
+    if (const int r = prepare_phase2_run(tr.data(), n_log2, exp, out.data(), bad_section, bad_index)) return r;
+    // the temporary exists only once the whole file is computed
+    TempOutput tmp(out_path);
+    if (tmp.fd() < 0 || !pwrite_all(tmp.fd(), out.data(), out.size(), 0) || !tmp.commit()) return KZGPOT_E_IO;
+    return 0;
+  });
+}
+
+}  // extern "C"

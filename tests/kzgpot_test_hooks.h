@@ -21,7 +21,7 @@ extern "C" {
 #define KZGPOT_FAULT_LAUNCH 1
 #define KZGPOT_FAULT_COLLECTIVE 2
 int kzgpot_comm_inject_fault(void* comm, int site, uint32_t at);
-/* Host-resource failure injection (csrc/capi.hip): from the (skip + 1)-th event of `site` on, every
+/* Host-resource failure injection (csrc/host_rt.hpp): from the (skip + 1)-th event of `site` on, every
  * such event in the process fails, until site 0 clears it:
  *   KZGPOT_HOST_FAULT_THREAD: a library host thread fails to start, as std::thread does with
  *   std::system_error(EAGAIN) under RLIMIT_NPROC; KZGPOT_HOST_FAULT_HOSTBUF: the file path's
@@ -30,7 +30,7 @@ int kzgpot_comm_inject_fault(void* comm, int site, uint32_t at);
 #define KZGPOT_HOST_FAULT_THREAD 1
 #define KZGPOT_HOST_FAULT_HOSTBUF 2
 int kzgpot_test_inject_host_fault(int site, long skip);
-/* The chunk plan of a host-buffer call of n points (csrc/capi.hip ChunkPlan): up to cap (offset,
+/* The chunk plan of a host-buffer call of n points (csrc/chunk_plan.hpp ChunkPlan): up to cap (offset,
  * count) pairs into spans; returns the number of chunks. streaming_consumer: the e2e output digest
  * reads the chunks as they land (its first chunk is small). */
 long kzgpot_test_chunk_plan(uint64_t n, int streaming_consumer, uint64_t* spans, long cap);

@@ -120,7 +120,7 @@ def test_chunked_host_path_first_bad(gpu, oracle_lib):
 
 @pytest.mark.parametrize("n", [(1 << 18), (1 << 18) + 1, 3 * (1 << 17) + 5, (1 << 21) + 777, (1 << 24) + 3])
 def test_host_chunk_schedule_boundaries(gpu, oracle_lib, n):
-    """run_host's chunk plan (csrc/capi.hip ChunkPlan; its tiling is checked on the CPU by
+    """run_host's chunk plan (csrc/chunk_plan.hpp ChunkPlan; its tiling is checked on the CPU by
     tests/test_host.py): up to 2^18 points one chunk; above, equal chunks of >= 2^17 points — here
     1, 3 and 4 chunks, the last a ragged 1 / 5 points — and from ~2^21 points a ramp: 2^17 points
     growing x4 to the chunk size, then halving back to 2^17, the ragged remainder in the middle

@@ -144,7 +144,7 @@ def test_streamed_digest_with_small_first_chunk(gpu, mode, n_log2, shards):
     """τG1 (2N - 1 points) and ατG1 run in several host chunks per shard, and with the output
     digest streaming from them each shard's first chunk is the small 2^16-point one (csrc/capi.hip
     run_host); with 2 shards the records reach the digest in file order only as far as both shards
-    have landed (preprocess_impl's cursor). Both digests equal hashlib's over the same bytes,
+    have landed (csrc/host_rt.hpp ShardCursor). Both digests equal hashlib's over the same bytes,
     τG1 / ατG1 equal the generator's; then bad points in the first chunk and in a later one: the
     first chunk's is reported."""
     n = 1 << n_log2

@@ -199,7 +199,7 @@ def test_load_phase1_short_file_is_size_error(kzgpot_mod):
 
 @pytest.mark.parametrize("streaming", [0, 1], ids=["plain", "digest_consumer"])
 def test_host_chunk_plan_tiles_the_call(kzgpot_mod, streaming):
-    """run_host's chunk plan (csrc/capi.hip ChunkPlan, through the test build's
+    """run_host's chunk plan (csrc/chunk_plan.hpp ChunkPlan, through the test build's
     kzgpot_test_chunk_plan): the chunks tile [0, n) in order with no gap or overlap, none exceeds
     the staging size (2^21 points), calls of 2^20 to 2^24 points get at least 8 chunks, and a long
     call starts and ends on 2^17-point chunks (so only those chunks' copies are exposed), ramping

@@ -1,11 +1,12 @@
 #!/usr/bin/env bash
-# Same-box comparison of host-buffer pipelines (csrc/capi.hip run_host / ChunkPlan): the product
+# Same-box comparison of host-buffer pipelines (csrc/capi.hip run_host, csrc/chunk_plan.hpp ChunkPlan): the product
 # build (A) against variant libraries build_exp_<V>/libkzgpot.so, alternating, two rounds, on G1 / G2
 # calls of several sizes (tools/host_api_trace.py). Variants measured: `old` = equal chunks (before
 # r06x); B / D / E = -DKZGPOT_CHUNK_END_LOG2 / -DKZGPOT_CHUNK_FLOOR_LOG2 = 17/18, 16/18, 17/19
 # (profiles/r06za_ab_plans); `two` = the product's two-slot pipeline beside a three-slot A
 # (profiles/r06zb_ab_slots). Build a variant by copying build/*.o to build_exp_<V>/ and rebuilding
-# capi.o there with the knobs.
+# capi.o there with the knobs (the one unit that includes chunk_plan.hpp; capi_test.o too if the
+# variant's test library is wanted).
 # Results: gpurun_out/ab_plans/<variant>_<kind><log2>_<round>.json
 set -e
 V=${VARIANTS:-A old}

@@ -1,4 +1,4 @@
-"""Fluid model of run_host's two-stream chunk pipeline (csrc/capi.hip ChunkPlan), used to choose the
+"""Fluid model of run_host's two-stream chunk pipeline (csrc/chunk_plan.hpp ChunkPlan), used to choose the
 chunk plan: the host thread copies chunk j in (blocking), launches it, then waits for chunk j - 1's
 kernel and copies its output out; kernels in flight share the GPU equally and last at least one
 block lifetime. Copies at the 56 GB/s the r06w trace shows for pageable 33 MB pieces.
