@@ -248,6 +248,51 @@ int kzgpot_prepare_phase2_buffer(const uint8_t* transcript, size_t len, uint32_t
 int kzgpot_prepare_phase2(const char* transcript_path, const char* out_path, uint32_t n_log2, uint32_t exp,
                           int* bad_section, int64_t* bad_index);
 
+/* ---------------------------------------------------------------- multi-scalar multiplication (KZG10 commit) */
+/* out = sum_{i<n} [s_i] P_i in G1 / G2: ark-ec VariableBaseMSM::multi_scalar_mul as ark-poly-commit
+ * 0.2 KZG10::commit runs it over powers_of_g (and powers_of_gamma_g for the blinding polynomial) —
+ * the one thing the reference's end_to_end_test_kzg (src/lib.rs:230-290) does with a loaded setup.
+ * One ark-uncompressed record out (96 / 192 B; the infinity record for an empty or vanishing sum).
+ *   scalars: n x 32 bytes, each a 256-bit unsigned integer, little-endian — the byte image of
+ *     ark-ff BigInteger256 (4 LE u64), what `coeff.into_repr()` gives. Used as INTEGERS: no range
+ *     check, no reduction mod r (2^256 - 1, r and 0 are legal); for points of the prime-order
+ *     subgroup that is ark's result.
+ *   bases: n packed ark-uncompressed records (what the codecs and the group FFT emit), range- and
+ *     flag-checked as the loaders check them (coordinate >= p: status 3; both SWFlags: 6; smallest
+ *     failing index; a rejected call writes nothing). An infinity record is legal and contributes
+ *     nothing. Not re-checked for curve or subgroup membership: off the curve the result is undefined.
+ *   KZGPOT_MSM_BASES_MONT: bases are the loaders' in-memory GroupAffine records instead
+ *     (KZGPOT_G1_ARK_MONT_BYTES / KZGPOT_G2_ARK_MONT_BYTES), so rows of Powers.powers_of_g go in
+ *     unchanged; a coordinate >= p gives status 3, a non-zero infinity byte is the point at infinity.
+ *   KZGPOT_MSM_WINDOW(c): window width override, 1 <= c <= 16, in flag bits 8..12; 0: the library
+ *     chooses (kzgpot_msm_window_bits).
+ * n = 0 gives the infinity record; n > 2^26, an unknown flag, a width above 16, or an override
+ * with n ceil(256 / c) >= 2^32 is KZGPOT_E_INVALID_ARG. */
+#define KZGPOT_MSM_BASES_MONT 0x1u
+#define KZGPOT_MSM_WINDOW(c) (((uint32_t)(c) & 0x1fu) << 8)
+/* Host only. The width c the library chooses for n points, a table:
+ *   n <  28416: 8    n <  55872: 9    n <  120384: 10   n <  238720: 11   n < 472064: 12
+ *   n < 1114113: 13  n < 2244609: 14  n < 3669568: 15   otherwise: 16
+ * Each threshold is the smallest n at which the cost model  n W + B + 43 (W max(min(n, 2^c), n / 64) + B / 64),
+ * W = ceil(256 / c), B = W c 2^(c-1) — bucket additions, bit-partial additions and one inversion
+ * (about 43 additions' worth) per 64-entry partial sum — prefers c to c - 1. */
+uint32_t kzgpot_msm_window_bits(uint64_t n);
+/* Host only. Bytes of device memory (d_work) the _dev calls below need for these flags; 0 for
+ * invalid arguments. Without a width override the size is monotone in n. */
+uint64_t kzgpot_msm_workspace(int g2, uint64_t n, uint32_t flags);
+/* Asynchronous on `stream`: d_bases, d_scalars (4-byte aligned), d_out (one record, 16-byte
+ * aligned) and d_work in HBM. d_bad_key as for kzgpot_g1_fft_dev (reset to all ones, lowered to
+ * (index << 8) | status by a malformed base, after which d_out is not written). */
+int kzgpot_g1_msm_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, uint32_t flags, void* d_work,
+                      uint64_t* d_bad_key, void* stream);
+int kzgpot_g2_msm_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, uint32_t flags, void* d_work,
+                      uint64_t* d_bad_key, void* stream);
+/* The same on host buffers, synchronous, on the current device. */
+int kzgpot_g1_msm(const uint8_t* bases, const uint8_t* scalars, uint64_t n, uint8_t* out, uint32_t flags,
+                  int64_t* first_bad);
+int kzgpot_g2_msm(const uint8_t* bases, const uint8_t* scalars, uint64_t n, uint8_t* out, uint32_t flags,
+                  int64_t* first_bad);
+
 /* ---------------------------------------------------------------- BN254 (config 5, next-row §8f 4) */
 /* No reference counterpart: the same path instantiated for ark-bn254 0.2 G1 (cofactor 1).
  * ark compressed (32 B: x LE, SWFlags bit7 PositiveY / bit6 Infinity in byte 31) → ark

@@ -1,5 +1,6 @@
-// Internal C++ interface between the C ABI (capi.hip, preprocess.hip, phase2.hip) and the kernels (codec_kernels.hip,
-// g1_kernels.hip; the device functions those two share are in codec_parts.hpp).
+// Internal C++ interface between the C ABI (capi.hip, preprocess.hip, phase2.hip, msm.hip) and the kernels
+// (codec_kernels.hip, g1_kernels.hip; the device functions those two share are in codec_parts.hpp, those of
+// fft_kernels.hip and msm_kernels.hip in group_parts.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -85,5 +86,16 @@ hipError_t launch_group_fft(bool g2, const void* d_in, uint32_t exp, void* d_out
                             const FftScalars& sc, void* d_work, unsigned long long* d_key, hipStream_t stream);
 // h[i] = tau_g1[m + i] - tau_g1[i], i < m - 1: ark G1 records in, pairing BE records out
 hipError_t launch_h_bases(const void* d_tau_g1, uint64_t m, void* d_out, hipStream_t stream);
+
+// multi-scalar multiplication (msm_kernels.hip): out = sum_i [s_i] P_i, one ark record. c: window
+// width 1..16; msm_workspace_bytes is 0 where (n, c) is not supported, and takes c = 0 for "the
+// library's choice, msm_window_bits(n)" (a size monotone in n; launch_msm wants the width itself).
+// Bases are ark records or (mont) in-memory GroupAffine records; scalars 8 LE words each.
+constexpr uint32_t kMsmChunk = 64;            // L: no lane sums more entries than this
+constexpr uint64_t kMsmMaxN = 1ull << 26;
+uint32_t msm_window_bits(uint64_t n);
+uint64_t msm_workspace_bytes(bool g2, uint64_t n, uint32_t c);
+hipError_t launch_msm(bool g2, const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, bool mont,
+                      uint32_t c, void* d_work, unsigned long long* d_key, hipStream_t stream);
 
 }  // namespace kzgpot

@@ -1,0 +1,89 @@
+// C ABI (include/kzgpot.h): the G1 / G2 multi-scalar multiplication of KZG10::commit
+// (kernels: msm_kernels.hip).
+#include "codec.hpp"
+#include "device_rt.hpp"
+#include "host_rt.hpp"
+
+using namespace kzgpot;
+
+namespace {
+
+constexpr uint32_t kMsmFlags = KZGPOT_MSM_BASES_MONT | KZGPOT_MSM_WINDOW(0x1f);
+
+// the override in the flags (0: the library chooses); false: invalid flags
+bool msm_override(uint32_t flags, uint32_t& c) {
+  c = (flags >> 8) & 0x1fu;
+  return !(flags & ~kMsmFlags) && c <= 16;
+}
+
+uint64_t base_record(bool g2, uint32_t flags) {
+  if (flags & KZGPOT_MSM_BASES_MONT) return g2 ? KZGPOT_G2_ARK_MONT_BYTES : KZGPOT_G1_ARK_MONT_BYTES;
+  return g2 ? 192 : 96;
+}
+
+// host_key (optional): receives the bad key once the sum is done
+int msm_dev(bool g2, const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, uint32_t flags, void* d_work,
+            uint64_t* d_bad_key, void* stream, uint64_t* host_key = nullptr) {
+  uint32_t c;
+  if (!msm_override(flags, c) || !msm_workspace_bytes(g2, n, c) || !d_out || !d_work || !d_bad_key || (n && (!d_bases || !d_scalars)))
+    return KZGPOT_E_INVALID_ARG;
+  const hipStream_t s = (hipStream_t)stream;
+  return launch_with_key(d_bad_key, s, [&](unsigned long long* key) {
+    return launch_msm(g2, d_bases, d_scalars, n, d_out, flags & KZGPOT_MSM_BASES_MONT, c ? c : msm_window_bits(n),
+                      d_work, key, s);
+  }, host_key);
+}
+
+int msm_host(bool g2, const uint8_t* bases, const uint8_t* scalars, uint64_t n, uint8_t* out, uint32_t flags,
+             int64_t* first_bad) {
+  if (first_bad) *first_bad = -1;
+  uint32_t c;
+  const uint64_t work_bytes = msm_override(flags, c) ? msm_workspace_bytes(g2, n, c) : 0;
+  if (!work_bytes || !out || (n && (!bases || !scalars))) return KZGPOT_E_INVALID_ARG;
+  if (device_count() <= 0) return KZGPOT_E_DEVICE;
+  DeviceGuard guard;
+  const uint64_t rec = base_record(g2, flags), out_bytes = g2 ? 192 : 96;
+  DevBuf d_bases, d_scalars, d_out, work, key;
+  if (d_bases.alloc(n * rec) || d_scalars.alloc(n * 32) || d_out.alloc(out_bytes) || work.alloc(work_bytes) ||
+      key.alloc(sizeof(uint64_t)))
+    return KZGPOT_E_DEVICE;
+  if (n) {
+    HIP_TRY(hipMemcpy(d_bases.p, bases, n * rec, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_scalars.p, scalars, n * 32, hipMemcpyHostToDevice));
+  }
+  uint64_t k;
+  if (const int r = msm_dev(g2, d_bases.p, d_scalars.p, n, d_out.p, flags, work.p, (uint64_t*)key.p, nullptr, &k))
+    return r;
+  if (k != kNoBad) return decode_key(k, first_bad);  // rejected: nothing is written
+  HIP_TRY(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* host only */
+uint32_t kzgpot_msm_window_bits(uint64_t n) { return msm_window_bits(n); }
+uint64_t kzgpot_msm_workspace(int g2, uint64_t n, uint32_t flags) {
+  uint32_t c;
+  return msm_override(flags, c) ? msm_workspace_bytes(g2 != 0, n, c) : 0;
+}
+int kzgpot_g1_msm_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, uint32_t flags, void* d_work,
+                      uint64_t* d_bad_key, void* stream) {
+  return api_guard([&] { return msm_dev(false, d_bases, d_scalars, n, d_out, flags, d_work, d_bad_key, stream); });
+}
+int kzgpot_g2_msm_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, uint32_t flags, void* d_work,
+                      uint64_t* d_bad_key, void* stream) {
+  return api_guard([&] { return msm_dev(true, d_bases, d_scalars, n, d_out, flags, d_work, d_bad_key, stream); });
+}
+int kzgpot_g1_msm(const uint8_t* bases, const uint8_t* scalars, uint64_t n, uint8_t* out, uint32_t flags,
+                  int64_t* first_bad) {
+  return api_guard([&] { return msm_host(false, bases, scalars, n, out, flags, first_bad); });
+}
+int kzgpot_g2_msm(const uint8_t* bases, const uint8_t* scalars, uint64_t n, uint8_t* out, uint32_t flags,
+                  int64_t* first_bad) {
+  return api_guard([&] { return msm_host(true, bases, scalars, n, out, flags, first_bad); });
+}
+
+}  // extern "C"

@@ -478,3 +478,81 @@ def prepare_phase2(transcript_path: str, out_path: str | None = None, n_log2: in
                                           n_log2, exp, ctypes.byref(sec), ctypes.byref(idx))
     if r:
         raise KzgPotError(r, idx.value, sec.value)
+
+
+# ------------------------------------------------------------------ multi-scalar multiplication, KZG10 commit
+MSM_BASES_MONT = 0x1  # bases are in-memory GroupAffine records (104 / 200 B) instead of ark records
+R_ORDER = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001  # the group order r
+
+
+def msm_flags(mont: bool = False, window: int = 0) -> int:
+    """KZGPOT_MSM_BASES_MONT | KZGPOT_MSM_WINDOW(window); window 0: the library chooses."""
+    if not 0 <= window <= 31:
+        raise ValueError(f"msm: window width {window}")
+    return (MSM_BASES_MONT if mont else 0) | (window << 8)
+
+
+def msm_window_bits(n: int) -> int:
+    """The window width the library chooses for n points (include/kzgpot.h states the formula)."""
+    return int(_lib.load().kzgpot_msm_window_bits(n))
+
+
+def msm_workspace(g2: bool, n: int, flags: int = 0) -> int:
+    return int(_lib.load().kzgpot_msm_workspace(int(g2), n, flags))
+
+
+def _scalar_bytes(scalars) -> bytes:
+    """32 n bytes: each scalar a 256-bit unsigned integer, little-endian (ark BigInteger256)."""
+    if isinstance(scalars, (bytes, bytearray, memoryview)):
+        return bytes(scalars)
+    return b"".join(int(s).to_bytes(32, "little") for s in scalars)
+
+
+def _msm(g2: bool, bases, scalars, mont: bool, window: int) -> CodecResult:
+    rec = (G2_ARK_MONT_BYTES if g2 else G1_ARK_MONT_BYTES) if mont else (192 if g2 else 96)
+    ptr, nbytes, keep = _buf(bases)
+    sc = _scalar_bytes(scalars)
+    if nbytes % rec or len(sc) != 32 * (nbytes // rec):
+        raise ValueError(f"msm: {nbytes} B of {rec}-B bases and {len(sc)} B of scalars")
+    out = ctypes.create_string_buffer(192 if g2 else 96)
+    fb = ctypes.c_int64(-1)
+    fn = _lib.load().kzgpot_g2_msm if g2 else _lib.load().kzgpot_g1_msm
+    ret = fn(ptr, sc, nbytes // rec, out, msm_flags(mont, window), ctypes.byref(fb))
+    del keep
+    if ret <= -100:
+        raise KzgPotError(ret)
+    return CodecResult(out.raw if ret == 0 else b"", ret, fb.value, None)
+
+
+def g1_msm(bases, scalars, mont: bool = False, window: int = 0) -> CodecResult:
+    """sum_i [s_i] P_i in G1 (ark `VariableBaseMSM::multi_scalar_mul`): `bases` packed ark-uncompressed
+    records (or, mont=True, in-memory GroupAffine records), `scalars` 32-byte little-endian
+    integers (bytes-like) or Python ints in [0, 2^256), used as integers. `out` is the one ark
+    record; a malformed base gives ret = -(status), first_bad = its index and out = b""."""
+    return _msm(False, bases, scalars, mont, window)
+
+
+def g2_msm(bases, scalars, mont: bool = False, window: int = 0) -> CodecResult:
+    return _msm(True, bases, scalars, mont, window)
+
+
+def kzg_commit(powers, coeffs, blinding=None) -> bytes:
+    """ark-poly-commit 0.2 `KZG10::commit(&powers, &p, hiding_bound, rng)` for a `Powers` or
+    `UniversalParams` from the loaders: [p(tau)]G + [q(tau)] gamma G as one MSM over
+    powers_of_g[:len(coeffs)] ‖ powers_of_gamma_g[:len(blinding)]. `coeffs` and `blinding` (the
+    random polynomial ark draws; None: not hiding) are ints mod r, lowest degree first; trailing
+    zeros are dropped as ark skips them. Returns the ark-uncompressed G1 record."""
+    import numpy as np
+
+    def trimmed(poly):
+        poly = [int(c) % R_ORDER for c in (poly or [])]
+        while poly and poly[-1] == 0:
+            poly.pop()
+        return poly
+
+    p, q = trimmed(coeffs), trimmed(blinding)
+    if len(p) > len(powers.powers_of_g) or len(q) > len(powers.powers_of_gamma_g):
+        raise ValueError(f"kzg_commit: degrees {len(p) - 1} / {len(q) - 1} exceed the powers supplied")
+    bases = np.concatenate([np.asarray(powers.powers_of_g[: len(p)], dtype=np.uint8).reshape(-1),
+                            np.asarray(powers.powers_of_gamma_g[: len(q)], dtype=np.uint8).reshape(-1)])
+    return _checked(g1_msm(bases, p + q, mont=True))

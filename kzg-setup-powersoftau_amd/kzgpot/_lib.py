@@ -60,6 +60,12 @@ SIGNATURES = {
     "kzgpot_g2_fft_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kzgpot_g1_fft": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, i64p]),
     "kzgpot_g2_fft": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, i64p]),
+    "kzgpot_msm_window_bits": (ctypes.c_uint32, [ctypes.c_uint64]),
+    "kzgpot_msm_workspace": (ctypes.c_uint64, [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]),
+    "kzgpot_g1_msm_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kzgpot_g2_msm_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kzgpot_g1_msm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, i64p]),
+    "kzgpot_g2_msm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, i64p]),
     "kzgpot_phase1radix_size": (ctypes.c_uint64, [ctypes.c_uint32]),
     "kzgpot_prepare_phase2_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, intp, i64p]),
     "kzgpot_prepare_phase2": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, intp, i64p]),

@@ -136,3 +136,40 @@ def g1_fft_dev(d_in, exp, d_out, key, **kw) -> torch.Tensor:
 
 def g2_fft_dev(d_in, exp, d_out, key, **kw) -> torch.Tensor:
     return group_fft_dev(True, d_in, exp, d_out, key, **kw)
+
+
+def msm_dev(g2: bool, d_bases: torch.Tensor, d_scalars: torch.Tensor, d_out: torch.Tensor, key: torch.Tensor,
+            mont: bool = False, window: int = 0, work: torch.Tensor | None = None) -> torch.Tensor:
+    """Asynchronous multi-scalar multiplication on device tensors (torch's current stream): n bases
+    (ark records, or in-memory GroupAffine records with mont=True), n 32-byte little-endian
+    scalars, one ark record into d_out. Allocates the workspace (kzgpot_msm_workspace bytes)
+    unless `work` is given; returns it — keep it alive until the stream has run the call."""
+    rec = ((200 if g2 else 104) if mont else (192 if g2 else 96))
+    n = d_scalars.numel() // 32
+    if d_scalars.numel() != 32 * n or d_bases.numel() != rec * n or d_out.numel() < (192 if g2 else 96):
+        raise ValueError(f"msm: bad buffer sizes {d_bases.numel()} / {d_scalars.numel()} / {d_out.numel()}")
+    if not (d_bases.is_cuda and d_scalars.is_cuda and d_out.is_cuda and key.is_cuda):
+        raise ValueError("msm_dev needs device tensors")
+    lib = _lib.load()
+    flags = (1 if mont else 0) | (window << 8)
+    need = int(lib.kzgpot_msm_workspace(int(g2), n, flags))
+    if need == 0:
+        raise ValueError(f"msm: n = {n} with window {window} is not supported")
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=d_out.device)
+    elif work.numel() < need:
+        raise ValueError(f"msm: workspace of {work.numel()} B, {need} needed")
+    fn = lib.kzgpot_g2_msm_dev if g2 else lib.kzgpot_g1_msm_dev
+    rc = fn(d_bases.data_ptr(), d_scalars.data_ptr(), n, d_out.data_ptr(), flags, work.data_ptr(), key.data_ptr(),
+            _stream())
+    if rc:
+        raise RuntimeError(f"msm: launch failed ({rc})")
+    return work
+
+
+def g1_msm_dev(d_bases, d_scalars, d_out, key, **kw) -> torch.Tensor:
+    return msm_dev(False, d_bases, d_scalars, d_out, key, **kw)
+
+
+def g2_msm_dev(d_bases, d_scalars, d_out, key, **kw) -> torch.Tensor:
+    return msm_dev(True, d_bases, d_scalars, d_out, key, **kw)

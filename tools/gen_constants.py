@@ -263,6 +263,7 @@ def main():
         "static constexpr uint32_t FP_ARK_WORD[12][14] = {"
         + ", ".join("{" + ", ".join(f"0x{v:08x}u" for v in limbs28((1 << (384 + 56 + 32 * k)) % P)) + "}"
                     for k in range(12)) + "};",
+        arr("FP_FROM_ARK", limbs28((1 << 400) % P), "2^400 mod p: fp_mul(x 2^384, .) = x R (ark-ff Montgomery form in, msm_kernels.hip)"),
         arr("FP_INV2", limbs28(mont(inv2))),
         arr("FP_BETA", limbs28(mont(beta))),
         arr("FP_PSI_CX1", limbs28(mont(cx[1]))),

@@ -32,6 +32,8 @@
 #   census        tools/microbench/bin/fpops_peak + tools/fpops/census.py
 #   lagrange      tools/lagrange_timing.py (group FFT launches at G1 2^16 / 2^20, G2 2^16 / 2^18, and
 #                 prepare_phase2 end to end at 2^21; one process)
+#   msm           tools/msm_timing.py (MSM launches at G1 2^16 / 2^20 / 2^22, G2 2^16 / 2^20, and the
+#                 all-equal-scalar row at 2^20; one process)
 set -o pipefail
 tag=${1:?usage: gpu_run.sh TAG STEP [STEP ...]}
 shift
@@ -80,6 +82,7 @@ for step in "$@"; do
             timeout -k 10 300 python3 -u tools/fpops/census.py --peaks ${o}_fpops_peak.txt > ${o}_fp_census.json \
               2> ${o}_fp_census.err ;;
     lagrange) timeout -k 10 500 python3 -u tools/lagrange_timing.py > ${o}_lagrange.json 2> ${o}_lagrange.err ;;
+    msm) timeout -k 10 500 python3 -u tools/msm_timing.py > ${o}_msm_timing.json 2> ${o}_msm_timing.err ;;
     *) echo "[gpu_run] unknown step $step" >&2; exit 2 ;;
   esac
   rc=$?
