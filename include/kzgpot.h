@@ -293,6 +293,63 @@ int kzgpot_g1_msm(const uint8_t* bases, const uint8_t* scalars, uint64_t n, uint
 int kzgpot_g2_msm(const uint8_t* bases, const uint8_t* scalars, uint64_t n, uint8_t* out, uint32_t flags,
                   int64_t* first_bad);
 
+/* ---------------------------------------------------------------- polynomial division over Fr, KZG10 open */
+/* For n coefficients c[0..n) of p, lowest degree first, and a point z: value = p(z) and the n - 1
+ * coefficients of the witness polynomial (p(x) - p(z)) / (x - z), as a tiled scan of the Horner
+ * recurrence H[j] = c[j] + z H[j+1] (value = H[0], quotient[j] = H[j+1]) on the GPU.
+ *   coeffs, z: 32-byte little-endian 256-bit integers (the byte image of BigInteger256), any value:
+ *     each is reduced mod r (2^256 - 1 is legal and means its residue).
+ *   quotient: (n - 1) x 32 bytes, value: 32 bytes, little-endian, canonical (below r). quotient may be
+ *     NULL: evaluate only. It must not overlap coeffs.
+ *   KZGPOT_POLY_TILE(t): coefficients per 256-lane block, 2^t with 8 <= t <= 12, in flag bits
+ *     16..19; 0: the library's tile (2^11). The result does not depend on it.
+ * n = 0 gives value 0; n = 1 gives value c[0] mod r and an empty quotient. n > 2^26 + 1, an unknown
+ * flag bit, a tile outside 8..12 or a NULL pointer where a count is non-zero is KZGPOT_E_INVALID_ARG. */
+#define KZGPOT_POLY_TILE(t) (((uint32_t)(t) & 0xfu) << 16)
+/* Host only. Bytes of device memory (d_work) the division needs (at least 256; monotone in n);
+ * 0 for invalid arguments. */
+uint64_t kzgpot_fr_poly_workspace(uint64_t n, uint32_t flags);
+/* Asynchronous on `stream`: d_coeffs, d_quotient and d_value (16-byte aligned) and d_work in HBM;
+ * z_le32 is read on the host before the call returns. */
+int kzgpot_fr_poly_divide_dev(const void* d_coeffs, uint64_t n, const uint8_t z_le32[32], void* d_quotient,
+                              void* d_value, uint32_t flags, void* d_work, void* stream);
+/* The same on host buffers, synchronous, on the current device. */
+int kzgpot_fr_poly_divide(const uint8_t* coeffs, uint64_t n, const uint8_t z_le32[32], uint8_t* quotient,
+                          uint8_t value_le32[32], uint32_t flags);
+
+/* ark-poly-commit 0.2 KZG10::open (compute_witness_polynomial, then open_with_witness_polynomial)
+ * for a polynomial p of n coefficients and, when hiding, the blinding polynomial b of n_blind
+ * coefficients that commit drew (n_blind = 0: ark's None). out, 160 bytes:
+ *   [0, 96)    w, an ark-uncompressed G1 record:
+ *              sum_{j<n-1} [q[j]] powers_of_g[j] + sum_{j<n_blind-1} [q_b[j]] powers_of_gamma_g[j],
+ *              q and q_b the witness polynomials of p and b at z
+ *   [96, 128)  value = p(z), little-endian, canonical
+ *   [128, 160) random_v = b(z), little-endian, canonical; zeros when n_blind = 0
+ * Both divisions run as above and w is ONE multi-scalar multiplication over the two base ranges and
+ * the two quotients laid end to end in the workspace; the quotients never leave HBM.
+ *   flags: KZGPOT_MSM_BASES_MONT and KZGPOT_MSM_WINDOW(c) as for the MSM (rows of
+ *     Powers.powers_of_g go in unchanged with the first), KZGPOT_POLY_TILE(t) as above.
+ *   bases: only the first n - 1 records of powers_of_g and n_blind - 1 of powers_of_gamma_g are read
+ *     (supplying that many is the caller's contract), checked as the MSM checks them. A rejected call
+ *     writes nothing; the index counts along the concatenation: i < n - 1 is in powers_of_g,
+ *     otherwise i - (n - 1) is in powers_of_gamma_g.
+ * n = 0 or 1 (and n_blind <= 1) gives the infinity record. Coefficients are used as given: ark
+ * trims trailing zeros first, which changes no output byte. KZGPOT_E_INVALID_ARG, before any device
+ * use: a NULL pointer where a count is non-zero, an unknown flag bit, a tile outside 8..12, n or
+ * n_blind above 2^26 + 1, or n - 1 + n_blind - 1 bases above what the MSM takes at that width. */
+/* Host only. Bytes of d_work for these arguments; 0 when they are invalid. Without a width
+ * override the size is monotone in n and in n_blind. */
+uint64_t kzgpot_kzg_open_workspace(uint64_t n, uint64_t n_blind, uint32_t flags);
+/* Asynchronous on `stream`: every d_ pointer in HBM, d_coeffs, d_blinding, d_out (160 B) and d_work
+ * 16-byte aligned. d_bad_key as for kzgpot_g1_msm_dev. */
+int kzgpot_g1_kzg_open_dev(const void* d_powers_of_g, const void* d_coeffs, uint64_t n, const void* d_powers_of_gamma_g,
+                           const void* d_blinding, uint64_t n_blind, const uint8_t z_le32[32], void* d_out,
+                           uint32_t flags, void* d_work, uint64_t* d_bad_key, void* stream);
+/* The same on host buffers, synchronous, on the current device. */
+int kzgpot_g1_kzg_open(const uint8_t* powers_of_g, const uint8_t* coeffs, uint64_t n, const uint8_t* powers_of_gamma_g,
+                       const uint8_t* blinding, uint64_t n_blind, const uint8_t z_le32[32], uint8_t out[160],
+                       uint32_t flags, int64_t* first_bad);
+
 /* ---------------------------------------------------------------- BN254 (config 5, next-row §8f 4) */
 /* No reference counterpart: the same path instantiated for ark-bn254 0.2 G1 (cofactor 1).
  * ark compressed (32 B: x LE, SWFlags bit7 PositiveY / bit6 Infinity in byte 31) → ark

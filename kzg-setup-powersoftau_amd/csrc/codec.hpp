@@ -98,4 +98,18 @@ uint64_t msm_workspace_bytes(bool g2, uint64_t n, uint32_t c);
 hipError_t launch_msm(bool g2, const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, bool mont,
                       uint32_t c, void* d_work, unsigned long long* d_key, hipStream_t stream);
 
+// polynomial division by (x - z) over Fr (poly_kernels.hip): value = p(z), and unless d_quotient
+// is null the n - 1 coefficients of (p(x) - p(z)) / (x - z). t: tile width 2^t, kPolyTileMin ..
+// kPolyTileMax. z_pow[k] = z^(2^k) in Fr Montgomery form (8 LE words), computed on the host
+// (open.hip) with csrc/fr.hpp.
+constexpr uint32_t kPolyTileMin = 8, kPolyTileMax = 12, kPolyTile = 11;
+constexpr uint64_t kPolyMaxN = (1ull << 26) + 1;
+constexpr int kPolyPowers = 64;  // entries of z_pow: the top level (at most the fourth) reads up to index 3 x 12 + 11
+uint64_t poly_workspace_bytes(uint64_t n, uint32_t t);
+hipError_t launch_poly_divide(const void* d_coeffs, uint64_t n, const uint32_t (*z_pow)[8], void* d_quotient,
+                              void* d_value, uint32_t t, void* d_work, hipStream_t stream);
+// KZG10::open's last step: the two evaluations (64 B at d_values) behind the proof's point, unless
+// the MSM's load rejected a base
+hipError_t launch_open_emit(const void* d_values, void* d_out64, const unsigned long long* d_key, hipStream_t stream);
+
 }  // namespace kzgpot

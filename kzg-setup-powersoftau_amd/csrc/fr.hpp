@@ -1,8 +1,9 @@
 // BLS12-381 scalar field Fr (the group order r) for the group FFT's twiddle factors: 8 x 32-bit
 // little-endian words, Montgomery form with R = 2^256, one CIOS multiply shared by the host
 // (domain root, the powers w^(2^k), m^-1: phase2.hip) and the device (k_fft_twiddles builds w^j from
-// those powers, fft_kernels.hip). Nothing here is hot: ~31 multiplies per twiddle against the 254
-// point doublings the twiddle then drives.
+// those powers, fft_kernels.hip). Nothing there is hot: ~31 multiplies per twiddle against the 254
+// point doublings the twiddle then drives. The polynomial division of KZG10 open
+// (poly_kernels.hip, open.hip) adds the rest of the field: add, sub, load and store.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,5 +66,82 @@ __host__ __device__ inline void fr_from_mont(fr& out, const fr& a) {
   fr one = {{1, 0, 0, 0, 0, 0, 0, 0}};
   fr_mul(out, a, one);
 }
+
+// ---------------------------------------------------------------- polynomial arithmetic (poly_kernels.hip, open.hip)
+// out = a + b mod r for a, b < r
+__host__ __device__ inline void fr_add(fr& out, const fr& a, const fr& b) {
+  uint32_t t[9];
+  uint64_t c = 0;
+  for (int i = 0; i < 8; i++) {
+    c += (uint64_t)a.v[i] + b.v[i];
+    t[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  t[8] = (uint32_t)c;
+  fr_cond_sub(out, t);
+}
+
+// out = a - b mod r for a, b < r
+__host__ __device__ inline void fr_sub(fr& out, const fr& a, const fr& b) {
+  uint32_t d[8];
+  int64_t br = 0;
+  for (int i = 0; i < 8; i++) {
+    const int64_t s = (int64_t)a.v[i] - (int64_t)b.v[i] + br;
+    d[i] = (uint32_t)s;
+    br = s >> 32;  // 0 or -1
+  }
+  const uint32_t mask = (uint32_t)br;  // all ones: a < b, add r back
+  uint64_t c = 0;
+  for (int i = 0; i < 8; i++) {
+    c += (uint64_t)d[i] + (FR_R[i] & mask);
+    out.v[i] = (uint32_t)c;
+    c >>= 32;
+  }
+}
+
+// R = 2^256 mod r (the Montgomery one) and R^2 mod r, by 256 and 512 doublings at compile time
+struct fr_radix {
+  uint32_t one[8], r2[8];
+};
+constexpr fr_radix fr_make_radix() {
+  fr_radix k = {};
+  uint32_t x[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < 512; i++) {  // x = 2^(i + 1) mod r
+    uint32_t t[9] = {}, d[8] = {}, c = 0;
+    for (int j = 0; j < 8; j++) {
+      t[j] = (x[j] << 1) | c;
+      c = x[j] >> 31;
+    }
+    t[8] = c;
+    int64_t br = 0;
+    for (int j = 0; j < 8; j++) {
+      const int64_t s = (int64_t)t[j] - (int64_t)FR_R[j] + br;
+      d[j] = (uint32_t)s;
+      br = s < 0 ? -1 : 0;
+    }
+    const bool ge = (int64_t)t[8] + br >= 0;
+    for (int j = 0; j < 8; j++) x[j] = ge ? d[j] : t[j];
+    if (i == 255)
+      for (int j = 0; j < 8; j++) k.one[j] = x[j];
+  }
+  for (int j = 0; j < 8; j++) k.r2[j] = x[j];
+  return k;
+}
+constexpr fr_radix FR_RADIX = fr_make_radix();
+
+// Load: any 256-bit integer a (8 LE words; 2^256 - 1 is legal and means its residue) -> the
+// Montgomery form of a mod r, as one multiplication by R^2 mod r. Bound: CIOS returns
+// (a b + m r) / R for some m < R before its conditional subtraction; with a < R = 2^256 and
+// b = R^2 mod r < r that is below a b / R + r < b + r < 2 r, which is what fr_cond_sub takes, so the
+// result is reduced although a itself may be as large as 2.2 r. Inside the loop the running value
+// stays below R + 2 r < 2^258 (each round adds at most (R + r) 2^32 before its shift by 2^32): it
+// fits the nine words and the transient tenth.
+__host__ __device__ inline void fr_load(fr& out, const fr& a) {
+  fr r2;
+  for (int i = 0; i < 8; i++) r2.v[i] = FR_RADIX.r2[i];
+  fr_mul(out, a, r2);
+}
+// Store: Montgomery form -> the canonical value below r (8 LE words: 32 little-endian bytes)
+__host__ __device__ inline void fr_store(fr& out, const fr& a) { fr_from_mont(out, a); }
 
 }  // namespace kzgpot

@@ -1,0 +1,196 @@
+// C ABI (include/kzgpot.h): division of a polynomial over Fr by (x - z) and ark-poly-commit's
+// KZG10::open on top of it — the witness polynomials by poly_kernels.hip, the proof's point by one
+// launch_msm (msm_kernels.hip) over both quotients. The quotients never leave HBM.
+#include <string.h>
+
+#include "codec.hpp"
+#include "device_rt.hpp"
+#include "fr.hpp"
+#include "host_rt.hpp"
+
+using namespace kzgpot;
+
+namespace {
+
+constexpr uint32_t kTileFlags = KZGPOT_POLY_TILE(0xf);
+constexpr uint32_t kOpenFlags = kTileFlags | KZGPOT_MSM_BASES_MONT | KZGPOT_MSM_WINDOW(0x1f);
+constexpr uint64_t kOutBytes = 160, kPointBytes = 96;
+
+// the tile width the flags ask for (0: the library's); false: an override outside 8 .. 12
+bool poly_tile(uint32_t flags, uint32_t& t) {
+  t = (flags >> 16) & 0xfu;
+  if (!t) t = kPolyTile;
+  return t >= kPolyTileMin && t <= kPolyTileMax;
+}
+
+// z^(2^k) in Montgomery form for k < kPolyPowers; z is any 256-bit integer, reduced by fr_load
+struct ZPowers {
+  uint32_t p[kPolyPowers][8];
+  explicit ZPowers(const uint8_t z_le32[32]) {
+    fr z;
+    for (int k = 0; k < 8; k++)
+      z.v[k] = (uint32_t)z_le32[4 * k] | (uint32_t)z_le32[4 * k + 1] << 8 | (uint32_t)z_le32[4 * k + 2] << 16 |
+               (uint32_t)z_le32[4 * k + 3] << 24;
+    fr_load(z, z);
+    for (int k = 0; k < kPolyPowers; k++) {
+      memcpy(p[k], z.v, sizeof z.v);
+      fr_mul(z, z, z);
+    }
+  }
+};
+
+// ---------------------------------------------------------------- division
+int poly_divide_dev(const void* d_coeffs, uint64_t n, const uint8_t* z, void* d_quotient, void* d_value, uint32_t flags,
+                    void* d_work, void* stream) {
+  uint32_t t;
+  if ((flags & ~kTileFlags) || !poly_tile(flags, t) || !poly_workspace_bytes(n, t) || !z || !d_value || !d_work ||
+      (n && !d_coeffs))
+    return KZGPOT_E_INVALID_ARG;
+  const ZPowers zp(z);
+  HIP_TRY(launch_poly_divide(d_coeffs, n, zp.p, d_quotient, d_value, t, d_work, (hipStream_t)stream));
+  return 0;
+}
+
+int poly_divide_host(const uint8_t* coeffs, uint64_t n, const uint8_t* z, uint8_t* quotient, uint8_t* value,
+                     uint32_t flags) {
+  uint32_t t;
+  const uint64_t work_bytes = !(flags & ~kTileFlags) && poly_tile(flags, t) ? poly_workspace_bytes(n, t) : 0;
+  if (!work_bytes || !z || !value || (n && !coeffs)) return KZGPOT_E_INVALID_ARG;
+  if (device_count() <= 0) return KZGPOT_E_DEVICE;
+  DeviceGuard guard;
+  const uint64_t nq = n ? n - 1 : 0;
+  DevBuf d_coeffs, d_quot, d_value, work;
+  if (d_coeffs.alloc(n * 32) || d_quot.alloc(nq * 32) || d_value.alloc(32) || work.alloc(work_bytes))
+    return KZGPOT_E_DEVICE;
+  if (n) HIP_TRY(hipMemcpy(d_coeffs.p, coeffs, n * 32, hipMemcpyHostToDevice));
+  if (const int r = poly_divide_dev(d_coeffs.p, n, z, quotient ? d_quot.p : nullptr, d_value.p, flags, work.p, nullptr))
+    return r;
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipMemcpy(value, d_value.p, 32, hipMemcpyDeviceToHost));
+  if (quotient && nq) HIP_TRY(hipMemcpy(quotient, d_quot.p, nq * 32, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---------------------------------------------------------------- open
+// Workspace: the two base ranges end to end (what the one MSM reads), the two quotients end to
+// end (its scalars), the two evaluations, the division's levels, the MSM's own workspace.
+struct OpenPlan {
+  uint32_t t, c;  // c: the width override, 0 for the library's
+  uint64_t nq, nb, rec;
+  uint64_t bases, scalars, values, poly, msm, bytes;  // byte offsets
+  bool ok;
+};
+constexpr uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
+OpenPlan open_plan(uint64_t n, uint64_t n_blind, uint32_t flags) {
+  OpenPlan p = {};
+  if ((flags & ~kOpenFlags) || !poly_tile(flags, p.t) || n > kPolyMaxN || n_blind > kPolyMaxN) return p;
+  p.c = (flags >> 8) & 0x1fu;
+  p.nq = n ? n - 1 : 0;
+  p.nb = n_blind ? n_blind - 1 : 0;
+  p.rec = (flags & KZGPOT_MSM_BASES_MONT) ? KZGPOT_G1_ARK_MONT_BYTES : kPointBytes;
+  const uint64_t msm_bytes = p.c > 16 ? 0 : msm_workspace_bytes(false, p.nq + p.nb, p.c);
+  if (!msm_bytes) return p;
+  uint64_t o = 0;
+  p.bases = o, o += align256((p.nq + p.nb) * p.rec);
+  p.scalars = o, o += align256((p.nq + p.nb) * 32);
+  p.values = o, o += 256;
+  p.poly = o, o += poly_workspace_bytes(n > n_blind ? n : n_blind, p.t);  // one division at a time
+  p.msm = o, o += msm_bytes;
+  p.bytes = o;
+  p.ok = true;
+  return p;
+}
+
+// host_key (optional): receives the bad key once the proof is done
+int open_dev(const void* d_powers_of_g, const void* d_coeffs, uint64_t n, const void* d_powers_of_gamma_g,
+             const void* d_blinding, uint64_t n_blind, const uint8_t* z, void* d_out, uint32_t flags, void* d_work,
+             uint64_t* d_bad_key, void* stream, uint64_t* host_key = nullptr) {
+  const OpenPlan p = open_plan(n, n_blind, flags);
+  if (!p.ok || !z || !d_out || !d_work || !d_bad_key || (n && !d_coeffs) || (n_blind && !d_blinding) ||
+      (p.nq && !d_powers_of_g) || (p.nb && !d_powers_of_gamma_g))
+    return KZGPOT_E_INVALID_ARG;
+  const ZPowers zp(z);
+  const hipStream_t s = (hipStream_t)stream;
+  uint8_t* w = (uint8_t*)d_work;
+  uint8_t *bases = w + p.bases, *scalars = w + p.scalars, *values = w + p.values;
+  const uint64_t total = p.nq + p.nb;
+  return launch_with_key(d_bad_key, s, [&](unsigned long long* key) -> hipError_t {
+    hipError_t e;
+    if ((e = hipMemsetAsync(values, 0, 64, s))) return e;  // no blinding polynomial: random_v = 0
+    if ((e = launch_poly_divide(d_coeffs, n, zp.p, scalars, values, p.t, w + p.poly, s))) return e;
+    if (n_blind && (e = launch_poly_divide(d_blinding, n_blind, zp.p, scalars + p.nq * 32, values + 32, p.t, w + p.poly, s)))
+      return e;
+    if (p.nq && (e = hipMemcpyAsync(bases, d_powers_of_g, p.nq * p.rec, hipMemcpyDeviceToDevice, s))) return e;
+    if (p.nb && (e = hipMemcpyAsync(bases + p.nq * p.rec, d_powers_of_gamma_g, p.nb * p.rec, hipMemcpyDeviceToDevice, s)))
+      return e;
+    if ((e = launch_msm(false, bases, scalars, total, d_out, flags & KZGPOT_MSM_BASES_MONT,
+                        p.c ? p.c : msm_window_bits(total), w + p.msm, key, s)))
+      return e;
+    return launch_open_emit(values, (uint8_t*)d_out + kPointBytes, key, s);
+  }, host_key);
+}
+
+int open_host(const uint8_t* powers_of_g, const uint8_t* coeffs, uint64_t n, const uint8_t* powers_of_gamma_g,
+              const uint8_t* blinding, uint64_t n_blind, const uint8_t* z, uint8_t* out, uint32_t flags,
+              int64_t* first_bad) {
+  if (first_bad) *first_bad = -1;
+  const OpenPlan p = open_plan(n, n_blind, flags);
+  if (!p.ok || !z || !out || (n && !coeffs) || (n_blind && !blinding) || (p.nq && !powers_of_g) ||
+      (p.nb && !powers_of_gamma_g))
+    return KZGPOT_E_INVALID_ARG;
+  if (device_count() <= 0) return KZGPOT_E_DEVICE;
+  DeviceGuard guard;
+  DevBuf d_pg, d_pgg, d_coeffs, d_blind, d_out, work, key;
+  if (d_pg.alloc(p.nq * p.rec) || d_pgg.alloc(p.nb * p.rec) || d_coeffs.alloc(n * 32) || d_blind.alloc(n_blind * 32) ||
+      d_out.alloc(kOutBytes) || work.alloc(p.bytes) || key.alloc(sizeof(uint64_t)))
+    return KZGPOT_E_DEVICE;
+  if (p.nq) HIP_TRY(hipMemcpy(d_pg.p, powers_of_g, p.nq * p.rec, hipMemcpyHostToDevice));
+  if (p.nb) HIP_TRY(hipMemcpy(d_pgg.p, powers_of_gamma_g, p.nb * p.rec, hipMemcpyHostToDevice));
+  if (n) HIP_TRY(hipMemcpy(d_coeffs.p, coeffs, n * 32, hipMemcpyHostToDevice));
+  if (n_blind) HIP_TRY(hipMemcpy(d_blind.p, blinding, n_blind * 32, hipMemcpyHostToDevice));
+  uint64_t k;
+  if (const int r = open_dev(d_pg.p, d_coeffs.p, n, d_pgg.p, d_blind.p, n_blind, z, d_out.p, flags, work.p,
+                             (uint64_t*)key.p, nullptr, &k))
+    return r;
+  if (k != kNoBad) return decode_key(k, first_bad);  // rejected: nothing is written
+  HIP_TRY(hipMemcpy(out, d_out.p, kOutBytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* host only */
+uint64_t kzgpot_fr_poly_workspace(uint64_t n, uint32_t flags) {
+  uint32_t t;
+  return !(flags & ~kTileFlags) && poly_tile(flags, t) ? poly_workspace_bytes(n, t) : 0;
+}
+uint64_t kzgpot_kzg_open_workspace(uint64_t n, uint64_t n_blind, uint32_t flags) {
+  return open_plan(n, n_blind, flags).bytes;
+}
+int kzgpot_fr_poly_divide_dev(const void* d_coeffs, uint64_t n, const uint8_t z_le32[32], void* d_quotient,
+                              void* d_value, uint32_t flags, void* d_work, void* stream) {
+  return api_guard([&] { return poly_divide_dev(d_coeffs, n, z_le32, d_quotient, d_value, flags, d_work, stream); });
+}
+int kzgpot_fr_poly_divide(const uint8_t* coeffs, uint64_t n, const uint8_t z_le32[32], uint8_t* quotient,
+                          uint8_t value_le32[32], uint32_t flags) {
+  return api_guard([&] { return poly_divide_host(coeffs, n, z_le32, quotient, value_le32, flags); });
+}
+int kzgpot_g1_kzg_open_dev(const void* d_powers_of_g, const void* d_coeffs, uint64_t n, const void* d_powers_of_gamma_g,
+                           const void* d_blinding, uint64_t n_blind, const uint8_t z_le32[32], void* d_out,
+                           uint32_t flags, void* d_work, uint64_t* d_bad_key, void* stream) {
+  return api_guard([&] {
+    return open_dev(d_powers_of_g, d_coeffs, n, d_powers_of_gamma_g, d_blinding, n_blind, z_le32, d_out, flags, d_work,
+                    d_bad_key, stream);
+  });
+}
+int kzgpot_g1_kzg_open(const uint8_t* powers_of_g, const uint8_t* coeffs, uint64_t n, const uint8_t* powers_of_gamma_g,
+                       const uint8_t* blinding, uint64_t n_blind, const uint8_t z_le32[32], uint8_t out[160],
+                       uint32_t flags, int64_t* first_bad) {
+  return api_guard([&] {
+    return open_host(powers_of_g, coeffs, n, powers_of_gamma_g, blinding, n_blind, z_le32, out, flags, first_bad);
+  });
+}
+
+}  // extern "C"

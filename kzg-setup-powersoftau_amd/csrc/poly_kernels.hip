@@ -1,0 +1,294 @@
+// Division of a polynomial over Fr by (x - z): the evaluation and the witness polynomial of
+// ark-poly-commit's KZG10::open (compute_witness_polynomial), DESIGN.md §11.
+//
+// For n coefficients c[0..n), lowest degree first, the suffix Horner values
+//   H[j] = sum_{k >= j} c[k] z^(k-j),      H[j] = c[j] + z H[j+1]
+// give p(z) = H[0] and the quotient (p(x) - p(z)) / (x - z) = sum_j H[j+1] x^j. The recurrence is
+// first-order linear, so it is a scan under (A, len) o (B, len') = A + z^len B:
+//
+//   level 0   the n coefficients in tiles of S = 2^t; a block of 256 lanes owns a tile, a lane a run
+//             of M = S / 256 consecutive coefficients
+//   up        lane: Horner over its run (multiplier z); block: a tree over the 256 run sums with
+//             multipliers z^M, z^2M, ... -> one sum A_b per tile. The tile sums are level 1's
+//             entries: the same problem with multiplier z^S. Repeated until a level fits one tile.
+//   down      from the top level: a block takes its carry H[(b+1) S] from the level above (zero at
+//             the top), lane 255 adds z^M times it to its run sum, a suffix scan over the run sums
+//             (8 steps, multipliers z^M .. z^128M) gives every lane its own carry, and Horner from
+//             that carry writes the H of the lane's run. Levels >= 1 overwrite their sums with
+//             their H (a block touches its own tile only; the carries come from the level above);
+//             level 0 writes H[j] as quotient coefficient j - 1 and H[0] as the value.
+//
+// One stream, no grid-wide synchronisation, no look-back, no spin-wait, no cooperative launch; every
+// loop's trip count is a compile-time constant. No lane does more than 2 M <= 32 Horner steps and
+// 8 scan steps. Evaluate-only (no quotient) runs the up passes and the top level's down pass alone.
+//
+// Memory: a lane's run is M x 32 B at a stride of M x 32 B, so tiles are staged through LDS: every
+// global load and store is one uint4 per lane at consecutive addresses, and a lane reads its run
+// from LDS at a stride of 2 M + 1 uint4 (one uint4 of padding per run: an odd stride, so the 16-byte
+// reads of neighbouring lanes fall into different banks). Level 0 reads 32 B per coefficient in
+// the up pass, reads them again and writes 32 B in the down pass: 96 B per coefficient; the upper
+// levels add 96 / S of that.
+//
+// Values are Montgomery (R = 2^256) between load and store: coefficients are 256-bit integers
+// reduced on the way in (fr_load, csrc/fr.hpp), the quotient and the value leave canonical.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "codec.hpp"
+#include "fr.hpp"
+
+namespace kzgpot {
+namespace {
+
+// y^(2^k) for this level's multiplier y = z^(S^level), k < 12, Montgomery form
+struct PolyPowers {
+  fr p[kPolyTileMax];
+};
+
+template <int T>
+struct Tile {
+  static constexpr int S = 1 << T, M = S / 256, RUN = 2 * M + 1;  // RUN: uint4 per lane, padded
+  static constexpr int SLOTS = 256 * RUN;
+  static constexpr int LOG2M = T - 8;
+};
+
+__device__ inline void tile_get(fr& a, const uint4* tile, int slot) {
+  const uint4 lo = tile[slot], hi = tile[slot + 1];
+  a.v[0] = lo.x, a.v[1] = lo.y, a.v[2] = lo.z, a.v[3] = lo.w;
+  a.v[4] = hi.x, a.v[5] = hi.y, a.v[6] = hi.z, a.v[7] = hi.w;
+}
+__device__ inline void tile_put(uint4* tile, int slot, const fr& a) {
+  tile[slot] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
+  tile[slot + 1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
+}
+// a lane's column of the 256 run sums (word-major: neighbouring lanes, neighbouring banks)
+__device__ inline void park(uint32_t (*rows)[256], uint32_t lane, const fr& a) {
+#pragma unroll
+  for (int k = 0; k < 8; k++) rows[k][lane] = a.v[k];
+}
+__device__ inline void unpark(fr& a, const uint32_t (*rows)[256], uint32_t lane) {
+#pragma unroll
+  for (int k = 0; k < 8; k++) a.v[k] = rows[k][lane];
+}
+__device__ inline void mul_add(fr& acc, const fr& x, const fr& y, const fr& c) {  // acc = x y + c
+  fr t;
+  fr_mul(t, x, y);
+  fr_add(acc, t, c);
+}
+
+// entries [blk S, (blk + 1) S) of `in` (n_in entries of 32 B; zero past the end) -> the padded tile
+template <int T>
+__device__ inline void stage_in(uint4* tile, const uint4* in, uint64_t blk, uint64_t n_in) {
+  using G = Tile<T>;
+  const uint64_t base = blk * (2 * G::S), end = 2 * n_in;
+#pragma unroll
+  for (int r = 0; r < 2 * G::M; r++) {
+    const int i = r * 256 + (int)threadIdx.x;
+    const uint64_t g = base + (uint64_t)i;
+    tile[i + (i >> (G::LOG2M + 1))] = g < end ? in[g] : make_uint4(0, 0, 0, 0);
+  }
+}
+
+// the lane's run sum: sum_k c[k] z^k over its M entries. Level 0 (raw) converts each entry to
+// Montgomery form and leaves it converted in the tile.
+template <int T>
+__device__ inline void run_sum(fr& acc, uint4* tile, bool raw, const fr& z) {
+  using G = Tile<T>;
+  const int s = (int)threadIdx.x * G::RUN;
+#pragma unroll 1
+  for (int k = G::M - 1; k >= 0; k--) {
+    fr c;
+    tile_get(c, tile, s + 2 * k);
+    if (raw) {
+      fr_load(c, c);
+      tile_put(tile, s + 2 * k, c);
+    }
+    if (k == G::M - 1) acc = c;
+    else mul_add(acc, acc, z, c);
+  }
+}
+
+// ---------------------------------------------------------------- up: one sum per tile
+template <int T>
+__global__ void __launch_bounds__(256) k_poly_up(const uint4* __restrict__ in, uint64_t n_in, int raw,
+                                                 uint32_t* __restrict__ sums, PolyPowers pw) {
+  using G = Tile<T>;
+  __shared__ uint4 tile[G::SLOTS];
+  __shared__ uint32_t rows[8][256];
+  const uint32_t tid = threadIdx.x;
+  stage_in<T>(tile, in, blockIdx.x, n_in);
+  __syncthreads();
+  fr acc;
+  run_sum<T>(acc, tile, raw != 0, pw.p[0]);
+  park(rows, tid, acc);
+  // a'[i] = a[2 i] + y a[2 i + 1], y = z^M, z^2M, ..: 128, 64, .. 1 live lanes
+#pragma unroll 1
+  for (int k = 0; k < 8; k++) {
+    const uint32_t live = 128u >> k;
+    __syncthreads();
+    fr lo, hi;
+    if (tid < live) {
+      unpark(lo, rows, 2 * tid);
+      unpark(hi, rows, 2 * tid + 1);
+    }
+    __syncthreads();
+    if (tid < live) {
+      mul_add(acc, hi, pw.p[G::LOG2M + k], lo);
+      park(rows, tid, acc);
+    }
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) sums[(uint64_t)blockIdx.x * 8 + k] = acc.v[k];
+  }
+}
+
+// ---------------------------------------------------------------- down: the H of one tile
+// carries: the level above's H (entry b + 1 is this tile's carry; none for the last tile).
+// level0: entries are raw integers, H[j] goes out canonical as quotient coefficient j - 1; other
+// levels write H[j] in Montgomery form at entry j (out may be in). out may be null (evaluate
+// only). value (optional): H[0], canonical, from block 0.
+template <int T>
+__global__ void __launch_bounds__(256) k_poly_down(const uint4* in, uint64_t n_in, int level0, const uint32_t* carries,
+                                                   uint4* out, uint32_t* __restrict__ value, PolyPowers pw) {
+  using G = Tile<T>;
+  __shared__ uint4 tile[G::SLOTS];
+  __shared__ uint32_t rows[8][256];
+  const uint32_t tid = threadIdx.x;
+  const uint64_t blk = blockIdx.x;
+  stage_in<T>(tile, in, blk, n_in);
+  __syncthreads();
+  const fr z = pw.p[0];
+  fr acc, carry = {{0, 0, 0, 0, 0, 0, 0, 0}};
+  run_sum<T>(acc, tile, level0 != 0, z);
+  if (tid == 255 && blk + 1 < gridDim.x) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) carry.v[k] = carries[(blk + 1) * 8 + k];
+    mul_add(acc, carry, pw.p[G::LOG2M], acc);
+  }
+  park(rows, tid, acc);
+  // suffix scan: after step k lane l holds sum_{j < 2^(k+1)} y^j a[l + j], y = z^M
+#pragma unroll 1
+  for (int k = 0; k < 8; k++) {
+    const uint32_t d = 1u << k;
+    __syncthreads();
+    fr nb;
+    if (tid + d < 256) unpark(nb, rows, tid + d);
+    __syncthreads();
+    if (tid + d < 256) {
+      mul_add(acc, nb, pw.p[G::LOG2M + k], acc);
+      park(rows, tid, acc);
+    }
+  }
+  __syncthreads();
+  fr h = carry;  // lane 255: the tile's carry; the others: the next lane's suffix sum
+  if (tid < 255) unpark(h, rows, tid + 1);
+  const int s = (int)tid * G::RUN;
+  fr o;
+#pragma unroll 1
+  for (int k = G::M - 1; k >= 0; k--) {
+    fr c;
+    tile_get(c, tile, s + 2 * k);
+    mul_add(h, h, z, c);
+    o = h;
+    if (level0) fr_store(o, h);
+    tile_put(tile, s + 2 * k, o);
+  }
+  if (value && blk == 0 && tid == 0) {
+    if (!level0) fr_store(o, h);
+#pragma unroll
+    for (int k = 0; k < 8; k++) value[k] = o.v[k];
+  }
+  if (!out) return;
+  __syncthreads();
+  const uint64_t shift = level0 ? 1 : 0;
+#pragma unroll
+  for (int r = 0; r < 2 * G::M; r++) {
+    const int i = r * 256 + (int)tid;
+    const uint64_t e = blk * G::S + (uint64_t)(i >> 1);
+    if (e >= shift && e < n_in) out[(e - shift) * 2 + (i & 1)] = tile[i + (i >> (G::LOG2M + 1))];
+  }
+}
+
+__global__ void __launch_bounds__(64) k_open_emit(const uint32_t* __restrict__ values, uint32_t* __restrict__ out,
+                                                  const unsigned long long* __restrict__ key) {
+  if (*key != ~0ull) return;
+  if (threadIdx.x < 16) out[threadIdx.x] = values[threadIdx.x];
+}
+
+constexpr uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
+
+// Level k has cnt[k] entries; level 0 is the caller's array, levels 1 .. top live in the workspace.
+struct PolyPlan {
+  uint32_t top;
+  uint64_t cnt[8], off[8], bytes;
+};
+PolyPlan poly_plan(uint64_t n, uint32_t t) {
+  PolyPlan p = {};
+  p.cnt[0] = n;
+  while (p.cnt[p.top] > ((uint64_t)1 << t)) {
+    p.cnt[p.top + 1] = (p.cnt[p.top] + ((uint64_t)1 << t) - 1) >> t;
+    p.top++;
+    p.off[p.top] = p.bytes;
+    p.bytes += align256(p.cnt[p.top] * 32);
+  }
+  if (!p.bytes) p.bytes = 256;  // a size of 0 means invalid arguments
+  return p;
+}
+// 2^26 + 1 entries in tiles of 2^8 leave 5 at level 3: cnt[] and the power table hold every level
+static_assert(((kPolyMaxN - 1) >> (3 * kPolyTileMin)) + 1 <= (1u << kPolyTileMin), "at most 4 levels");
+static_assert(3 * kPolyTileMax + kPolyTileMax <= kPolyPowers, "z_pow holds the top level's powers");
+
+template <int T>
+hipError_t launch(const PolyPlan& p, const void* d_coeffs, const uint32_t (*z_pow)[8], void* d_quotient, void* d_value,
+                  void* d_work, hipStream_t s) {
+  uint8_t* w = (uint8_t*)d_work;
+  auto level = [&](uint32_t k) -> void* { return k ? (void*)(w + p.off[k]) : const_cast<void*>(d_coeffs); };
+  auto powers = [&](uint32_t k) {
+    PolyPowers pw;
+    for (uint32_t j = 0; j < kPolyTileMax; j++)
+      for (int i = 0; i < 8; i++) pw.p[j].v[i] = z_pow[k * T + j][i];
+    return pw;
+  };
+  auto tiles = [&](uint32_t k) { return dim3((unsigned)((p.cnt[k] + (1u << T) - 1) >> T)); };
+  for (uint32_t k = 0; k < p.top; k++)
+    hipLaunchKernelGGL(k_poly_up<T>, tiles(k), dim3(256), 0, s, (const uint4*)level(k), p.cnt[k], k == 0 ? 1 : 0,
+                       (uint32_t*)level(k + 1), powers(k));
+  for (uint32_t k = p.top + 1; k-- > 0;) {
+    const bool last = k == 0 || !d_quotient;  // evaluate only: the top level has the value
+    hipLaunchKernelGGL(k_poly_down<T>, tiles(k), dim3(256), 0, s, (const uint4*)level(k), p.cnt[k], k == 0 ? 1 : 0,
+                       k < p.top ? (const uint32_t*)level(k + 1) : nullptr,
+                       (uint4*)(k ? (d_quotient ? level(k) : nullptr) : d_quotient), last ? (uint32_t*)d_value : nullptr,
+                       powers(k));
+    if (last) break;
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+uint64_t poly_workspace_bytes(uint64_t n, uint32_t t) {
+  if (n > kPolyMaxN || t < kPolyTileMin || t > kPolyTileMax) return 0;
+  return poly_plan(n, t).bytes;
+}
+
+hipError_t launch_poly_divide(const void* d_coeffs, uint64_t n, const uint32_t (*z_pow)[8], void* d_quotient,
+                              void* d_value, uint32_t t, void* d_work, hipStream_t stream) {
+  if (!poly_workspace_bytes(n, t)) return hipErrorInvalidValue;
+  if (n == 0) return hipMemsetAsync(d_value, 0, 32, stream);  // the zero polynomial
+  const PolyPlan p = poly_plan(n, t);
+  switch (t) {
+    case 8: return launch<8>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);
+    case 9: return launch<9>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);
+    case 10: return launch<10>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);
+    case 11: return launch<11>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);
+    default: return launch<12>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);
+  }
+}
+
+hipError_t launch_open_emit(const void* d_values, void* d_out64, const unsigned long long* d_key, hipStream_t stream) {
+  hipLaunchKernelGGL(k_open_emit, dim3(1), dim3(64), 0, stream, (const uint32_t*)d_values, (uint32_t*)d_out64, d_key);
+  return hipGetLastError();
+}
+
+}  // namespace kzgpot

@@ -536,6 +536,14 @@ def g2_msm(bases, scalars, mont: bool = False, window: int = 0) -> CodecResult:
     return _msm(True, bases, scalars, mont, window)
 
 
+def _trimmed(poly) -> list:
+    """Coefficients reduced mod r, without the trailing zeros (ark's DensePolynomial invariant)."""
+    poly = [int(c) % R_ORDER for c in (poly or [])]
+    while poly and poly[-1] == 0:
+        poly.pop()
+    return poly
+
+
 def kzg_commit(powers, coeffs, blinding=None) -> bytes:
     """ark-poly-commit 0.2 `KZG10::commit(&powers, &p, hiding_bound, rng)` for a `Powers` or
     `UniversalParams` from the loaders: [p(tau)]G + [q(tau)] gamma G as one MSM over
@@ -544,15 +552,100 @@ def kzg_commit(powers, coeffs, blinding=None) -> bytes:
     zeros are dropped as ark skips them. Returns the ark-uncompressed G1 record."""
     import numpy as np
 
-    def trimmed(poly):
-        poly = [int(c) % R_ORDER for c in (poly or [])]
-        while poly and poly[-1] == 0:
-            poly.pop()
-        return poly
-
-    p, q = trimmed(coeffs), trimmed(blinding)
+    p, q = _trimmed(coeffs), _trimmed(blinding)
     if len(p) > len(powers.powers_of_g) or len(q) > len(powers.powers_of_gamma_g):
         raise ValueError(f"kzg_commit: degrees {len(p) - 1} / {len(q) - 1} exceed the powers supplied")
     bases = np.concatenate([np.asarray(powers.powers_of_g[: len(p)], dtype=np.uint8).reshape(-1),
                             np.asarray(powers.powers_of_gamma_g[: len(q)], dtype=np.uint8).reshape(-1)])
     return _checked(g1_msm(bases, p + q, mont=True))
+
+
+# ------------------------------------------------------------------ polynomial division over Fr, KZG10 open
+def poly_flags(tile: int = 0) -> int:
+    """KZGPOT_POLY_TILE(tile): 2^tile coefficients per block, 8 <= tile <= 12; 0: the library's tile."""
+    if not 0 <= tile <= 15:
+        raise ValueError(f"poly: tile {tile}")
+    return tile << 16
+
+
+def fr_poly_workspace(n: int, flags: int = 0) -> int:
+    return int(_lib.load().kzgpot_fr_poly_workspace(n, flags))
+
+
+def kzg_open_workspace(n: int, n_blind: int = 0, flags: int = 0) -> int:
+    return int(_lib.load().kzgpot_kzg_open_workspace(n, n_blind, flags))
+
+
+def _fr_bytes(z) -> bytes:
+    return int(z).to_bytes(32, "little")
+
+
+def fr_poly_divide(coeffs, z, tile: int = 0, want_quotient: bool = True):
+    """(quotient_bytes, value) of p(x) = sum coeffs[i] x^i divided by (x - z) on the GPU: value =
+    p(z) as an int below r, quotient_bytes the len(coeffs) - 1 canonical 32-byte little-endian
+    coefficients of (p(x) - p(z)) / (x - z). `coeffs` are 32-byte little-endian integers
+    (bytes-like) or Python ints in [0, 2^256), `z` an int in [0, 2^256); all are reduced mod r."""
+    sc = _scalar_bytes(coeffs)
+    if len(sc) % 32:
+        raise ValueError(f"fr_poly_divide: {len(sc)} B of coefficients")
+    n = len(sc) // 32
+    quot = ctypes.create_string_buffer(max(1, 32 * (n - 1))) if want_quotient else None
+    value = ctypes.create_string_buffer(32)
+    r = _lib.load().kzgpot_fr_poly_divide(sc, n, _fr_bytes(z), quot, value, poly_flags(tile))
+    if r:
+        raise KzgPotError(r)
+    return (quot.raw[: 32 * max(0, n - 1)] if want_quotient else None), int.from_bytes(value.raw, "little")
+
+
+def kzg_evaluate(coeffs, z) -> int:
+    """p(z) mod r on the GPU: what the reference's end_to_end_test_kzg gets from `p.evaluate(&point)`."""
+    return fr_poly_divide(coeffs, z, want_quotient=False)[1]
+
+
+@dataclass
+class KzgProof:
+    """ark-poly-commit 0.2 `kzg10::Proof` with the evaluation it proves: `w` the ark-uncompressed
+    G1 record, `random_v` the blinding polynomial's evaluation (None: not hiding), `value` = p(z)."""
+    w: bytes
+    random_v: int | None
+    value: int
+
+
+def g1_kzg_open(powers_of_g, coeffs, powers_of_gamma_g, blinding, z, mont: bool = False, window: int = 0,
+                tile: int = 0) -> CodecResult:
+    """kzgpot_g1_kzg_open on packed records and coefficients as given (no trimming): `out` is the
+    160 bytes w ‖ value ‖ random_v; a malformed base gives ret = -(status), first_bad = its index
+    along powers_of_g[:n - 1] ‖ powers_of_gamma_g[:n_blind - 1] and out = b""."""
+    rec = G1_ARK_MONT_BYTES if mont else 96
+    p, q = _scalar_bytes(coeffs), _scalar_bytes(blinding if blinding is not None else b"")
+    pg_ptr, pg_bytes, keep1 = _buf(powers_of_g)
+    pgg_ptr, pgg_bytes, keep2 = _buf(powers_of_gamma_g)
+    n, nb = len(p) // 32, len(q) // 32
+    if len(p) % 32 or len(q) % 32 or pg_bytes < rec * max(0, n - 1) or pgg_bytes < rec * max(0, nb - 1):
+        raise ValueError(f"kzg open: {n} / {nb} coefficients over {pg_bytes} / {pgg_bytes} B of {rec}-B bases")
+    out = ctypes.create_string_buffer(160)
+    fb = ctypes.c_int64(-1)
+    ret = _lib.load().kzgpot_g1_kzg_open(pg_ptr, p, n, pgg_ptr, q, nb, _fr_bytes(z), out,
+                                         msm_flags(mont, window) | poly_flags(tile), ctypes.byref(fb))
+    del keep1, keep2
+    if ret <= -100:
+        raise KzgPotError(ret)
+    return CodecResult(out.raw if ret == 0 else b"", ret, fb.value, None)
+
+
+def kzg_open(powers, coeffs, z, blinding=None, window: int = 0, tile: int = 0) -> KzgProof:
+    """ark-poly-commit 0.2 `KZG10::open(&powers, &p, point, &rand)` for a `Powers` or
+    `UniversalParams` from the loaders: both witness polynomials on the GPU and
+    w = [q(tau)]G + [q_b(tau)] gamma G as one MSM over powers_of_g ‖ powers_of_gamma_g. `coeffs` and
+    `blinding` (the polynomial commit drew; None: not hiding) are ints mod r, lowest degree
+    first, as kzg_commit takes them; trailing zeros are dropped as ark does."""
+    import numpy as np
+
+    p, q = _trimmed(coeffs), _trimmed(blinding)
+    if len(p) > len(powers.powers_of_g) or len(q) > len(powers.powers_of_gamma_g):
+        raise ValueError(f"kzg_open: degrees {len(p) - 1} / {len(q) - 1} exceed the powers supplied")
+    rows = lambda a, k: np.asarray(a[: max(0, k - 1)], dtype=np.uint8).reshape(-1)  # noqa: E731
+    out = _checked(g1_kzg_open(rows(powers.powers_of_g, len(p)), p, rows(powers.powers_of_gamma_g, len(q)), q, z,
+                               mont=True, window=window, tile=tile))
+    return KzgProof(out[:96], int.from_bytes(out[128:], "little") if blinding is not None else None,
+                    int.from_bytes(out[96:128], "little"))

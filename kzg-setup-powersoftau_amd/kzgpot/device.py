@@ -173,3 +173,68 @@ def g1_msm_dev(d_bases, d_scalars, d_out, key, **kw) -> torch.Tensor:
 
 def g2_msm_dev(d_bases, d_scalars, d_out, key, **kw) -> torch.Tensor:
     return msm_dev(True, d_bases, d_scalars, d_out, key, **kw)
+
+
+def _work(need: int, work: torch.Tensor | None, device, what: str) -> torch.Tensor:
+    if work is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    if work.numel() < need:
+        raise ValueError(f"{what}: workspace of {work.numel()} B, {need} needed")
+    return work
+
+
+def fr_poly_divide_dev(d_coeffs: torch.Tensor, z: int, d_quotient: torch.Tensor | None, d_value: torch.Tensor,
+                       tile: int = 0, work: torch.Tensor | None = None) -> torch.Tensor:
+    """Asynchronous division by (x - z) on device tensors (torch's current stream): n 32-byte
+    little-endian coefficients in, 32 (n - 1) bytes of quotient (None: evaluate only) and the 32-byte
+    value out. Allocates the workspace (kzgpot_fr_poly_workspace bytes) unless `work` is given;
+    returns it — keep it alive until the stream has run the call."""
+    n = d_coeffs.numel() // 32
+    if d_coeffs.numel() != 32 * n or d_value.numel() < 32 or (d_quotient is not None and d_quotient.numel() < 32 * (n - 1)):
+        raise ValueError(f"poly divide: bad buffer sizes {d_coeffs.numel()} / {d_value.numel()}")
+    if not (d_coeffs.is_cuda and d_value.is_cuda and (d_quotient is None or d_quotient.is_cuda)):
+        raise ValueError("fr_poly_divide_dev needs device tensors")
+    lib = _lib.load()
+    flags = tile << 16
+    need = int(lib.kzgpot_fr_poly_workspace(n, flags))
+    if need == 0:
+        raise ValueError(f"poly divide: n = {n} with tile {tile} is not supported")
+    work = _work(need, work, d_value.device, "poly divide")
+    rc = lib.kzgpot_fr_poly_divide_dev(d_coeffs.data_ptr(), n, int(z).to_bytes(32, "little"),
+                                       d_quotient.data_ptr() if d_quotient is not None else None, d_value.data_ptr(),
+                                       flags, work.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"poly divide: launch failed ({rc})")
+    return work
+
+
+def g1_kzg_open_dev(d_powers_of_g: torch.Tensor, d_coeffs: torch.Tensor, z: int, d_out: torch.Tensor, key: torch.Tensor,
+                    d_powers_of_gamma_g: torch.Tensor | None = None, d_blinding: torch.Tensor | None = None,
+                    mont: bool = False, window: int = 0, tile: int = 0, work: torch.Tensor | None = None) -> torch.Tensor:
+    """Asynchronous KZG10 open on device tensors (torch's current stream): the coefficients of p
+    (and of the blinding polynomial), at least n - 1 (n_blind - 1) base records, 160 bytes
+    (w ‖ value ‖ random_v) into d_out. Allocates the workspace (kzgpot_kzg_open_workspace bytes)
+    unless `work` is given; returns it — keep it alive until the stream has run the call."""
+    rec = 104 if mont else 96
+    n = d_coeffs.numel() // 32
+    nb = d_blinding.numel() // 32 if d_blinding is not None else 0
+    pgg = d_powers_of_gamma_g.numel() if d_powers_of_gamma_g is not None else 0
+    if (d_coeffs.numel() != 32 * n or (nb and d_blinding.numel() != 32 * nb) or d_out.numel() < 160
+            or d_powers_of_g.numel() < rec * max(0, n - 1) or pgg < rec * max(0, nb - 1)):
+        raise ValueError(f"kzg open: bad buffer sizes {d_powers_of_g.numel()} / {d_coeffs.numel()} / {pgg} / {d_out.numel()}")
+    tensors = [d_powers_of_g, d_coeffs, d_out, key] + [t for t in (d_powers_of_gamma_g, d_blinding) if t is not None]
+    if not all(t.is_cuda for t in tensors):
+        raise ValueError("g1_kzg_open_dev needs device tensors")
+    lib = _lib.load()
+    flags = (1 if mont else 0) | (window << 8) | (tile << 16)
+    need = int(lib.kzgpot_kzg_open_workspace(n, nb, flags))
+    if need == 0:
+        raise ValueError(f"kzg open: n = {n}, n_blind = {nb} with window {window}, tile {tile} is not supported")
+    work = _work(need, work, d_out.device, "kzg open")
+    rc = lib.kzgpot_g1_kzg_open_dev(d_powers_of_g.data_ptr(), d_coeffs.data_ptr(), n,
+                                    d_powers_of_gamma_g.data_ptr() if d_powers_of_gamma_g is not None else None,
+                                    d_blinding.data_ptr() if nb else None, nb, int(z).to_bytes(32, "little"),
+                                    d_out.data_ptr(), flags, work.data_ptr(), key.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"kzg open: launch failed ({rc})")
+    return work

@@ -34,6 +34,8 @@
 #                 prepare_phase2 end to end at 2^21; one process)
 #   msm           tools/msm_timing.py (MSM launches at G1 2^16 / 2^20 / 2^22, G2 2^16 / 2^20, and the
 #                 all-equal-scalar row at 2^20; one process)
+#   open          tools/open_timing.py (the polynomial division at 2^20 / 2^24 against a copy of its bytes,
+#                 KZG10 open at 2^20 and the MSM alone over the same bases; one process)
 set -o pipefail
 tag=${1:?usage: gpu_run.sh TAG STEP [STEP ...]}
 shift
@@ -83,6 +85,7 @@ for step in "$@"; do
               2> ${o}_fp_census.err ;;
     lagrange) timeout -k 10 500 python3 -u tools/lagrange_timing.py > ${o}_lagrange.json 2> ${o}_lagrange.err ;;
     msm) timeout -k 10 500 python3 -u tools/msm_timing.py > ${o}_msm_timing.json 2> ${o}_msm_timing.err ;;
+    open) timeout -k 10 500 python3 -u tools/open_timing.py > ${o}_open_timing.json 2> ${o}_open_timing.err ;;
     *) echo "[gpu_run] unknown step $step" >&2; exit 2 ;;
   esac
   rc=$?
