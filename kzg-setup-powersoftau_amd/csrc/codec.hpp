@@ -6,11 +6,13 @@
 #include <stdint.h>
 
 #include "../../include/kzgpot.h"
+#include "fr.hpp"
 
 namespace kzgpot {
 
 constexpr int kBlock = 256;  // 4 waves; one point per lane
 inline unsigned grid_for(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }  // blocks for n points
+constexpr uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }  // every workspace region's size
 
 // G1Phase1 / G2Phase1: read_g1 / read_g2 straight into the in-memory GroupAffine (load_phase1) —
 // the transcode kernel in place on the input staging buffer, then the loader kernel. Host-buffer
@@ -73,12 +75,12 @@ hipError_t launch_codec(CodecOp op, const void* d_in, void* d_out, uint64_t n, u
                         unsigned long long* d_first_bad, uint8_t* d_status, hipStream_t stream);
 
 // group FFT (fft_kernels.hip). The scalars of one transform, computed on the host (phase2.hip) with
-// csrc/fr.hpp: pw[k] = w^(+-2^k) and one in Fr Montgomery form (8 LE words, R = 2^256), minv = 1/m
-// canonical. d_work: fft_workspace_bytes = the twiddle table (fft_twiddle_bytes), then the work buffer.
+// csrc/fr.hpp and passed to k_fft_twiddles as they are. d_work: fft_workspace_bytes = the twiddle
+// table (fft_twiddle_bytes), then the work buffer.
 struct FftScalars {
-  uint32_t pw[31][8];
-  uint32_t one[8];
-  uint32_t minv[8];
+  fr pw[31];  // w^(+-2^k) in Montgomery form, k < exp - 1 (the rest unused)
+  fr one;     // Montgomery 1
+  fr minv;    // 1/m, canonical
 };
 uint64_t fft_twiddle_bytes(uint32_t exp);
 uint64_t fft_workspace_bytes(bool g2, uint32_t exp);
@@ -93,6 +95,12 @@ hipError_t launch_h_bases(const void* d_tau_g1, uint64_t m, void* d_out, hipStre
 // Bases are ark records or (mont) in-memory GroupAffine records; scalars 8 LE words each.
 constexpr uint32_t kMsmChunk = 64;            // L: no lane sums more entries than this
 constexpr uint64_t kMsmMaxN = 1ull << 26;
+constexpr uint32_t kMsmWindowMax = 16;
+// KZGPOT_MSM_WINDOW(c) in the flags: c = 0 (the library chooses) or the width; false: above kMsmWindowMax
+inline bool msm_window_flag(uint32_t flags, uint32_t& c) {
+  c = (flags >> 8) & 0x1fu;
+  return c <= kMsmWindowMax;
+}
 uint32_t msm_window_bits(uint64_t n);
 uint64_t msm_workspace_bytes(bool g2, uint64_t n, uint32_t c);
 hipError_t launch_msm(bool g2, const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, bool mont,
@@ -100,13 +108,18 @@ hipError_t launch_msm(bool g2, const void* d_bases, const void* d_scalars, uint6
 
 // polynomial division by (x - z) over Fr (poly_kernels.hip): value = p(z), and unless d_quotient
 // is null the n - 1 coefficients of (p(x) - p(z)) / (x - z). t: tile width 2^t, kPolyTileMin ..
-// kPolyTileMax. z_pow[k] = z^(2^k) in Fr Montgomery form (8 LE words), computed on the host
-// (open.hip) with csrc/fr.hpp.
+// kPolyTileMax. z_pow.p[k] = z^(2^k), computed on the host (open.hip) with csrc/fr.hpp.
 constexpr uint32_t kPolyTileMin = 8, kPolyTileMax = 12, kPolyTile = 11;
+// KZGPOT_POLY_TILE(t) in the flags: t, or the library's for 0; false: outside kPolyTileMin .. kPolyTileMax
+inline bool poly_tile_flag(uint32_t flags, uint32_t& t) {
+  t = (flags >> 16) & 0xfu;
+  if (!t) t = kPolyTile;
+  return t >= kPolyTileMin && t <= kPolyTileMax;
+}
 constexpr uint64_t kPolyMaxN = (1ull << 26) + 1;
 constexpr int kPolyPowers = 64;  // entries of z_pow: the top level (at most the fourth) reads up to index 3 x 12 + 11
 uint64_t poly_workspace_bytes(uint64_t n, uint32_t t);
-hipError_t launch_poly_divide(const void* d_coeffs, uint64_t n, const uint32_t (*z_pow)[8], void* d_quotient,
+hipError_t launch_poly_divide(const void* d_coeffs, uint64_t n, const fr_powers<kPolyPowers>& z_pow, void* d_quotient,
                               void* d_value, uint32_t t, void* d_work, hipStream_t stream);
 // KZG10::open's last step: the two evaluations (64 B at d_values) behind the proof's point, unless
 // the MSM's load rejected a base

@@ -11,10 +11,7 @@ namespace {
 constexpr uint32_t kMsmFlags = KZGPOT_MSM_BASES_MONT | KZGPOT_MSM_WINDOW(0x1f);
 
 // the override in the flags (0: the library chooses); false: invalid flags
-bool msm_override(uint32_t flags, uint32_t& c) {
-  c = (flags >> 8) & 0x1fu;
-  return !(flags & ~kMsmFlags) && c <= 16;
-}
+bool msm_override(uint32_t flags, uint32_t& c) { return msm_window_flag(flags, c) && !(flags & ~kMsmFlags); }
 
 uint64_t base_record(bool g2, uint32_t flags) {
   if (flags & KZGPOT_MSM_BASES_MONT) return g2 ? KZGPOT_G2_ARK_MONT_BYTES : KZGPOT_G1_ARK_MONT_BYTES;

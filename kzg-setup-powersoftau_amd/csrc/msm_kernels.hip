@@ -332,8 +332,6 @@ __global__ void __launch_bounds__(64) k_msm_final(const uint32_t* __restrict__ p
 }
 
 // ---------------------------------------------------------------- plan
-constexpr uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
-
 // Workspace layout for (g2, n, c). Partial sums ping-pong between two regions A and B of the
 // pool behind the n bases. A level with `in` entries has at most min(in, in / L + NB) chunks
 // (ceil(x / L) <= x, and <= x / L + 1 per non-empty bucket), so the regions are sized by
@@ -348,7 +346,7 @@ struct MsmPlan {
 };
 MsmPlan msm_plan(bool g2, uint64_t n, uint32_t c) {
   MsmPlan p = {};
-  if (n > kMsmMaxN || c < 1 || c > 16) return p;
+  if (n > kMsmMaxN || c < 1 || c > kMsmWindowMax) return p;
   p.c = c;
   p.nwin = (256 + c - 1) / c;
   p.nb = p.nwin << c;

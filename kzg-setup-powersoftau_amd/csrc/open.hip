@@ -1,11 +1,9 @@
 // C ABI (include/kzgpot.h): division of a polynomial over Fr by (x - z) and ark-poly-commit's
 // KZG10::open on top of it — the witness polynomials by poly_kernels.hip, the proof's point by one
-// launch_msm (msm_kernels.hip) over both quotients. The quotients never leave HBM.
-#include <string.h>
-
+// launch_msm (msm_kernels.hip) over both quotients. The quotients never leave HBM. The powers of z
+// that the division's kernels read come from the host side of csrc/fr.hpp.
 #include "codec.hpp"
 #include "device_rt.hpp"
-#include "fr.hpp"
 #include "host_rt.hpp"
 
 using namespace kzgpot;
@@ -16,45 +14,29 @@ constexpr uint32_t kTileFlags = KZGPOT_POLY_TILE(0xf);
 constexpr uint32_t kOpenFlags = kTileFlags | KZGPOT_MSM_BASES_MONT | KZGPOT_MSM_WINDOW(0x1f);
 constexpr uint64_t kOutBytes = 160, kPointBytes = 96;
 
-// the tile width the flags ask for (0: the library's); false: an override outside 8 .. 12
-bool poly_tile(uint32_t flags, uint32_t& t) {
-  t = (flags >> 16) & 0xfu;
-  if (!t) t = kPolyTile;
-  return t >= kPolyTileMin && t <= kPolyTileMax;
+// z^(2^k) for k < kPolyPowers; z is any 256-bit integer
+fr_powers<kPolyPowers> z_powers(const uint8_t z_le32[32]) {
+  fr_powers<kPolyPowers> zp;
+  fr_fill_powers(zp.p, fr_from_le32(z_le32));
+  return zp;
 }
-
-// z^(2^k) in Montgomery form for k < kPolyPowers; z is any 256-bit integer, reduced by fr_load
-struct ZPowers {
-  uint32_t p[kPolyPowers][8];
-  explicit ZPowers(const uint8_t z_le32[32]) {
-    fr z;
-    for (int k = 0; k < 8; k++)
-      z.v[k] = (uint32_t)z_le32[4 * k] | (uint32_t)z_le32[4 * k + 1] << 8 | (uint32_t)z_le32[4 * k + 2] << 16 |
-               (uint32_t)z_le32[4 * k + 3] << 24;
-    fr_load(z, z);
-    for (int k = 0; k < kPolyPowers; k++) {
-      memcpy(p[k], z.v, sizeof z.v);
-      fr_mul(z, z, z);
-    }
-  }
-};
 
 // ---------------------------------------------------------------- division
 int poly_divide_dev(const void* d_coeffs, uint64_t n, const uint8_t* z, void* d_quotient, void* d_value, uint32_t flags,
                     void* d_work, void* stream) {
   uint32_t t;
-  if ((flags & ~kTileFlags) || !poly_tile(flags, t) || !poly_workspace_bytes(n, t) || !z || !d_value || !d_work ||
+  if ((flags & ~kTileFlags) || !poly_tile_flag(flags, t) || !poly_workspace_bytes(n, t) || !z || !d_value || !d_work ||
       (n && !d_coeffs))
     return KZGPOT_E_INVALID_ARG;
-  const ZPowers zp(z);
-  HIP_TRY(launch_poly_divide(d_coeffs, n, zp.p, d_quotient, d_value, t, d_work, (hipStream_t)stream));
+  const fr_powers<kPolyPowers> zp = z_powers(z);
+  HIP_TRY(launch_poly_divide(d_coeffs, n, zp, d_quotient, d_value, t, d_work, (hipStream_t)stream));
   return 0;
 }
 
 int poly_divide_host(const uint8_t* coeffs, uint64_t n, const uint8_t* z, uint8_t* quotient, uint8_t* value,
                      uint32_t flags) {
   uint32_t t;
-  const uint64_t work_bytes = !(flags & ~kTileFlags) && poly_tile(flags, t) ? poly_workspace_bytes(n, t) : 0;
+  const uint64_t work_bytes = !(flags & ~kTileFlags) && poly_tile_flag(flags, t) ? poly_workspace_bytes(n, t) : 0;
   if (!work_bytes || !z || !value || (n && !coeffs)) return KZGPOT_E_INVALID_ARG;
   if (device_count() <= 0) return KZGPOT_E_DEVICE;
   DeviceGuard guard;
@@ -80,15 +62,13 @@ struct OpenPlan {
   uint64_t bases, scalars, values, poly, msm, bytes;  // byte offsets
   bool ok;
 };
-constexpr uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
 OpenPlan open_plan(uint64_t n, uint64_t n_blind, uint32_t flags) {
   OpenPlan p = {};
-  if ((flags & ~kOpenFlags) || !poly_tile(flags, p.t) || n > kPolyMaxN || n_blind > kPolyMaxN) return p;
-  p.c = (flags >> 8) & 0x1fu;
+  if ((flags & ~kOpenFlags) || !poly_tile_flag(flags, p.t) || n > kPolyMaxN || n_blind > kPolyMaxN) return p;
   p.nq = n ? n - 1 : 0;
   p.nb = n_blind ? n_blind - 1 : 0;
   p.rec = (flags & KZGPOT_MSM_BASES_MONT) ? KZGPOT_G1_ARK_MONT_BYTES : kPointBytes;
-  const uint64_t msm_bytes = p.c > 16 ? 0 : msm_workspace_bytes(false, p.nq + p.nb, p.c);
+  const uint64_t msm_bytes = msm_window_flag(flags, p.c) ? msm_workspace_bytes(false, p.nq + p.nb, p.c) : 0;
   if (!msm_bytes) return p;
   uint64_t o = 0;
   p.bases = o, o += align256((p.nq + p.nb) * p.rec);
@@ -109,7 +89,7 @@ int open_dev(const void* d_powers_of_g, const void* d_coeffs, uint64_t n, const 
   if (!p.ok || !z || !d_out || !d_work || !d_bad_key || (n && !d_coeffs) || (n_blind && !d_blinding) ||
       (p.nq && !d_powers_of_g) || (p.nb && !d_powers_of_gamma_g))
     return KZGPOT_E_INVALID_ARG;
-  const ZPowers zp(z);
+  const fr_powers<kPolyPowers> zp = z_powers(z);
   const hipStream_t s = (hipStream_t)stream;
   uint8_t* w = (uint8_t*)d_work;
   uint8_t *bases = w + p.bases, *scalars = w + p.scalars, *values = w + p.values;
@@ -117,8 +97,8 @@ int open_dev(const void* d_powers_of_g, const void* d_coeffs, uint64_t n, const 
   return launch_with_key(d_bad_key, s, [&](unsigned long long* key) -> hipError_t {
     hipError_t e;
     if ((e = hipMemsetAsync(values, 0, 64, s))) return e;  // no blinding polynomial: random_v = 0
-    if ((e = launch_poly_divide(d_coeffs, n, zp.p, scalars, values, p.t, w + p.poly, s))) return e;
-    if (n_blind && (e = launch_poly_divide(d_blinding, n_blind, zp.p, scalars + p.nq * 32, values + 32, p.t, w + p.poly, s)))
+    if ((e = launch_poly_divide(d_coeffs, n, zp, scalars, values, p.t, w + p.poly, s))) return e;
+    if (n_blind && (e = launch_poly_divide(d_blinding, n_blind, zp, scalars + p.nq * 32, values + 32, p.t, w + p.poly, s)))
       return e;
     if (p.nq && (e = hipMemcpyAsync(bases, d_powers_of_g, p.nq * p.rec, hipMemcpyDeviceToDevice, s))) return e;
     if (p.nb && (e = hipMemcpyAsync(bases + p.nq * p.rec, d_powers_of_gamma_g, p.nb * p.rec, hipMemcpyDeviceToDevice, s)))
@@ -164,7 +144,7 @@ extern "C" {
 /* host only */
 uint64_t kzgpot_fr_poly_workspace(uint64_t n, uint32_t flags) {
   uint32_t t;
-  return !(flags & ~kTileFlags) && poly_tile(flags, t) ? poly_workspace_bytes(n, t) : 0;
+  return !(flags & ~kTileFlags) && poly_tile_flag(flags, t) ? poly_workspace_bytes(n, t) : 0;
 }
 uint64_t kzgpot_kzg_open_workspace(uint64_t n, uint64_t n_blind, uint32_t flags) {
   return open_plan(n, n_blind, flags).bytes;

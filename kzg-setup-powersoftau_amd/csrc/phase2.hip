@@ -1,91 +1,23 @@
-// C ABI (include/kzgpot.h): the G1 / G2 group FFT and the phase1radix2m (Lagrange-basis) writer,
-// with the host-side Fr arithmetic (csrc/fr.hpp) that computes each transform's scalars.
-#include <string.h>
-
+// C ABI (include/kzgpot.h): the G1 / G2 group FFT and the phase1radix2m (Lagrange-basis) writer.
+// Each transform's scalars come from the host side of csrc/fr.hpp.
 #include "accumulator.hpp"
 #include "codec.hpp"
 #include "device_rt.hpp"
-#include "fr.hpp"
 #include "host_rt.hpp"
 
 using namespace kzgpot;
 
 namespace {
 
-// Fr on the host (csrc/fr.hpp's multiply): R = 2^256 mod r and R^2 by repeated doubling
-struct FrHost {
-  fr one, r2;
-  FrHost() {
-    fr x = {{1, 0, 0, 0, 0, 0, 0, 0}};
-    for (int i = 0; i < 512; i++) {  // x = 2^(i + 1) mod r
-      uint32_t t[9];
-      uint32_t c = 0;
-      for (int k = 0; k < 8; k++) {
-        t[k] = (x.v[k] << 1) | c;
-        c = x.v[k] >> 31;
-      }
-      t[8] = c;
-      fr_cond_sub(x, t);
-      if (i == 255) one = x;
-    }
-    r2 = x;
-  }
-  fr to_mont(uint64_t a) const {
-    fr x = {{(uint32_t)a, (uint32_t)(a >> 32), 0, 0, 0, 0, 0, 0}}, y;
-    fr_mul(y, x, r2);
-    return y;
-  }
-  fr pow(const fr& base, const uint32_t (&e)[8]) const {  // base in Montgomery form, e any 256-bit exponent
-    fr acc = one;
-    for (int b = 255; b >= 0; b--) {
-      fr_mul(acc, acc, acc);
-      if ((e[b >> 5] >> (b & 31)) & 1) fr_mul(acc, acc, base);
-    }
-    return acc;
-  }
-};
-const FrHost& fr_host() {
-  static const FrHost h;
-  return h;
-}
-
-// w_m = 7^((r - 1) / 2^exp) in Montgomery form: bellman's omega for the domain of size 2^exp
-// (its root_of_unity = 7^((r-1)/2^32) squared 32 - exp times), and ark-poly's Radix2EvaluationDomain's
-fr domain_root_mont(uint32_t exp) {
-  uint32_t rm1[9], e[8];
-  for (int k = 0; k < 8; k++) rm1[k] = FR_R[k];
-  rm1[0] -= 1;  // r is odd
-  rm1[8] = 0;
-  for (int k = 0; k < 8; k++) e[k] = (uint32_t)((((uint64_t)rm1[k + 1] << 32) | rm1[k]) >> exp);  // exp <= 32
-  const FrHost& h = fr_host();
-  return h.pow(h.to_mont(7), e);
-}
-
 // The scalars of one transform of size m = 2^exp: the powers w^(+-2^k) (the inverse uses
-// w^-1 = w^(m-1)) and 1/m = m^(r-2)
+// w^-1 = w^(m-1)) and 1/m
 void fft_scalars(uint32_t exp, bool inverse, FftScalars& sc) {
-  const FrHost& h = fr_host();
   const uint64_t m = (uint64_t)1 << exp;
-  fr w = domain_root_mont(exp);
-  if (inverse) {
-    const uint32_t e[8] = {(uint32_t)(m - 1), 0, 0, 0, 0, 0, 0, 0};  // m - 1 < 2^32
-    w = h.pow(w, e);
-  }
-  for (int k = 0; k < 31; k++) {
-    memcpy(sc.pw[k], w.v, sizeof w.v);
-    fr_mul(w, w, w);
-  }
-  memcpy(sc.one, h.one.v, sizeof sc.one);
-  uint32_t rm2[8];
-  int64_t br = -2;
-  for (int k = 0; k < 8; k++) {
-    const int64_t s = (int64_t)FR_R[k] + br;
-    rm2[k] = (uint32_t)s;
-    br = s >> 32;
-  }
-  fr minv;
-  fr_from_mont(minv, h.pow(h.to_mont(m), rm2));
-  memcpy(sc.minv, minv.v, sizeof sc.minv);
+  fr w = fr_domain_root(exp);
+  if (inverse) w = fr_pow(w, fr{{(uint32_t)(m - 1), 0, 0, 0, 0, 0, 0, 0}});  // m - 1 < 2^32
+  fr_fill_powers(sc.pw, w);
+  sc.one = fr_one();
+  fr_store(sc.minv, fr_inv(fr_from_u64(m)));
 }
 
 constexpr uint32_t kFftFlags = KZGPOT_FFT_INVERSE | KZGPOT_FFT_OUT_PAIRING;
@@ -195,10 +127,7 @@ extern "C" {
 int kzgpot_fr_domain_root(uint32_t exp, uint8_t root_be32[32]) {
   if (exp > 32 || !root_be32) return KZGPOT_E_INVALID_ARG;
   return api_guard([&] {
-    fr w;
-    fr_from_mont(w, domain_root_mont(exp));
-    for (int k = 0; k < 8; k++)
-      for (int b = 0; b < 4; b++) root_be32[31 - 4 * k - b] = (uint8_t)(w.v[k] >> (8 * b));
+    fr_to_be32(root_be32, fr_domain_root(exp));
     return 0;
   });
 }

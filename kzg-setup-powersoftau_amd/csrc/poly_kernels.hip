@@ -35,7 +35,6 @@
 #include <stdint.h>
 
 #include "codec.hpp"
-#include "fr.hpp"
 
 namespace kzgpot {
 namespace {
@@ -216,8 +215,6 @@ __global__ void __launch_bounds__(64) k_open_emit(const uint32_t* __restrict__ v
   if (threadIdx.x < 16) out[threadIdx.x] = values[threadIdx.x];
 }
 
-constexpr uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
-
 // Level k has cnt[k] entries; level 0 is the caller's array, levels 1 .. top live in the workspace.
 struct PolyPlan {
   uint32_t top;
@@ -240,14 +237,13 @@ static_assert(((kPolyMaxN - 1) >> (3 * kPolyTileMin)) + 1 <= (1u << kPolyTileMin
 static_assert(3 * kPolyTileMax + kPolyTileMax <= kPolyPowers, "z_pow holds the top level's powers");
 
 template <int T>
-hipError_t launch(const PolyPlan& p, const void* d_coeffs, const uint32_t (*z_pow)[8], void* d_quotient, void* d_value,
-                  void* d_work, hipStream_t s) {
+hipError_t launch(const PolyPlan& p, const void* d_coeffs, const fr_powers<kPolyPowers>& z_pow, void* d_quotient,
+                  void* d_value, void* d_work, hipStream_t s) {
   uint8_t* w = (uint8_t*)d_work;
   auto level = [&](uint32_t k) -> void* { return k ? (void*)(w + p.off[k]) : const_cast<void*>(d_coeffs); };
   auto powers = [&](uint32_t k) {
     PolyPowers pw;
-    for (uint32_t j = 0; j < kPolyTileMax; j++)
-      for (int i = 0; i < 8; i++) pw.p[j].v[i] = z_pow[k * T + j][i];
+    for (uint32_t j = 0; j < kPolyTileMax; j++) pw.p[j] = z_pow.p[k * T + j];
     return pw;
   };
   auto tiles = [&](uint32_t k) { return dim3((unsigned)((p.cnt[k] + (1u << T) - 1) >> T)); };
@@ -272,7 +268,7 @@ uint64_t poly_workspace_bytes(uint64_t n, uint32_t t) {
   return poly_plan(n, t).bytes;
 }
 
-hipError_t launch_poly_divide(const void* d_coeffs, uint64_t n, const uint32_t (*z_pow)[8], void* d_quotient,
+hipError_t launch_poly_divide(const void* d_coeffs, uint64_t n, const fr_powers<kPolyPowers>& z_pow, void* d_quotient,
                               void* d_value, uint32_t t, void* d_work, hipStream_t stream) {
   if (!poly_workspace_bytes(n, t)) return hipErrorInvalidValue;
   if (n == 0) return hipMemsetAsync(d_value, 0, 32, stream);  // the zero polynomial
