@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(kBlock) k_bn254_g1_decompress(const uint4* __r
 hipError_t launch_bn254(const void* d_in, void* d_out, uint64_t n, unsigned long long* d_first_bad, uint8_t* d_status,
                         hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_bn254_g1_decompress, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const uint4*)d_in,
+  hipLaunchKernelGGL(k_bn254_g1_decompress, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, stream, (const uint4*)d_in,
                      (uint4*)d_out, n, d_first_bad, d_status);
   return hipGetLastError();
 }

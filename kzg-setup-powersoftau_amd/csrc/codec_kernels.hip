@@ -286,7 +286,7 @@ k_g2_check(const uint4* __restrict__ in, uint4* __restrict__ out, uint64_t n, ui
 hipError_t launch_codec(CodecOp op, const void* d_in, void* d_out, uint64_t n, uint32_t flags,
                         unsigned long long* d_first_bad, uint8_t* d_status, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  const dim3 grid(grid_for(n)), block(kBlock);
+  const dim3 grid(grid_for(n, kBlock)), block(kBlock);
   const uint4* in = (const uint4*)d_in;
   uint4* out = (uint4*)d_out;
   const bool checked = !(flags & KZGPOT_NO_SUBGROUP_CHECK);

@@ -191,7 +191,7 @@ __global__ void __launch_bounds__(kBlock) k_g1_check(const uint4* __restrict__ i
 hipError_t launch_g1(CodecOp op, const uint4* in, uint4* out, uint64_t n, uint32_t flags,
                      unsigned long long* d_first_bad, uint8_t* d_status, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  const dim3 grid(grid_for(n)), block(kBlock);
+  const dim3 grid(grid_for(n, kBlock)), block(kBlock);
   const bool checked = !(flags & KZGPOT_NO_SUBGROUP_CHECK);
   switch (op) {
     case CodecOp::G1Decompress:

@@ -22,6 +22,8 @@ struct Geo {
   // butterflies per block: 2 NW LDS rows per lane = 28 KB either way (4 blocks = 8 waves per CU)
   static constexpr int BLOCK = NC == 1 ? 256 : 128;
 };
+static_assert(Geo<fp>::ROWS == kWorkRowsG1 && Geo<fp2>::ROWS == kWorkRowsG2, "the plans' row counts (plans.hpp)");
+static_assert(Geo<fp>::INF_ROW == kWorkRowsG1 - 1 && Geo<fp2>::INF_ROW == kWorkRowsG2 - 1, "the last row marks infinity");
 
 // ---------------------------------------------------------------- field helpers, both fields
 KZG_DEV fp& comp(fp& a, int) { return a; }

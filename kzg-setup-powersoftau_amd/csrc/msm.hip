@@ -8,21 +8,11 @@ using namespace kzgpot;
 
 namespace {
 
-constexpr uint32_t kMsmFlags = KZGPOT_MSM_BASES_MONT | KZGPOT_MSM_WINDOW(0x1f);
-
-// the override in the flags (0: the library chooses); false: invalid flags
-bool msm_override(uint32_t flags, uint32_t& c) { return msm_window_flag(flags, c) && !(flags & ~kMsmFlags); }
-
-uint64_t base_record(bool g2, uint32_t flags) {
-  if (flags & KZGPOT_MSM_BASES_MONT) return g2 ? KZGPOT_G2_ARK_MONT_BYTES : KZGPOT_G1_ARK_MONT_BYTES;
-  return g2 ? 192 : 96;
-}
-
 // host_key (optional): receives the bad key once the sum is done
 int msm_dev(bool g2, const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, uint32_t flags, void* d_work,
             uint64_t* d_bad_key, void* stream, uint64_t* host_key = nullptr) {
   uint32_t c;
-  if (!msm_override(flags, c) || !msm_workspace_bytes(g2, n, c) || !d_out || !d_work || !d_bad_key || (n && (!d_bases || !d_scalars)))
+  if (!msm_flags(flags, c) || !msm_workspace_bytes(g2, n, c) || !d_out || !d_work || !d_bad_key || (n && (!d_bases || !d_scalars)))
     return KZGPOT_E_INVALID_ARG;
   const hipStream_t s = (hipStream_t)stream;
   return launch_with_key(d_bad_key, s, [&](unsigned long long* key) {
@@ -35,11 +25,11 @@ int msm_host(bool g2, const uint8_t* bases, const uint8_t* scalars, uint64_t n, 
              int64_t* first_bad) {
   if (first_bad) *first_bad = -1;
   uint32_t c;
-  const uint64_t work_bytes = msm_override(flags, c) ? msm_workspace_bytes(g2, n, c) : 0;
+  const uint64_t work_bytes = msm_flags(flags, c) ? msm_workspace_bytes(g2, n, c) : 0;
   if (!work_bytes || !out || (n && (!bases || !scalars))) return KZGPOT_E_INVALID_ARG;
   if (device_count() <= 0) return KZGPOT_E_DEVICE;
   DeviceGuard guard;
-  const uint64_t rec = base_record(g2, flags), out_bytes = g2 ? 192 : 96;
+  const uint64_t rec = base_record(g2, flags & KZGPOT_MSM_BASES_MONT), out_bytes = point_record(g2);
   DevBuf d_bases, d_scalars, d_out, work, key;
   if (d_bases.alloc(n * rec) || d_scalars.alloc(n * 32) || d_out.alloc(out_bytes) || work.alloc(work_bytes) ||
       key.alloc(sizeof(uint64_t)))
@@ -64,7 +54,7 @@ extern "C" {
 uint32_t kzgpot_msm_window_bits(uint64_t n) { return msm_window_bits(n); }
 uint64_t kzgpot_msm_workspace(int g2, uint64_t n, uint32_t flags) {
   uint32_t c;
-  return msm_override(flags, c) ? msm_workspace_bytes(g2 != 0, n, c) : 0;
+  return msm_flags(flags, c) ? msm_workspace_bytes(g2 != 0, n, c) : 0;
 }
 int kzgpot_g1_msm_dev(const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, uint32_t flags, void* d_work,
                       uint64_t* d_bad_key, void* stream) {

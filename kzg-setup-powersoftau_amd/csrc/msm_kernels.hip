@@ -28,6 +28,9 @@
 // most 2/3 of an addition per entry of a full chunk, a lane's serial work is bounded by 64
 // additions, and n = 2^26 needs K = 5 levels. A chunk of one entry is copied, not inverted.
 //
+// Where every launch reads and writes inside the workspace, and the list of k_msm_sum launches, is
+// msm_plan's (plans.hpp, checked on the CPU by tests/test_plan_units.py).
+//
 // Between two additions X, Y and Z go through fp_canon, so every jac_madd starts from a canonical
 // accumulator (or Z = 0) and a canonical base: tests/test_field_bounds_msm.py.
 #include <hip/hip_runtime.h>
@@ -41,7 +44,6 @@ namespace {
 constexpr uint32_t L = kMsmChunk;
 constexpr uint32_t kNoBucket = ~0u;
 constexpr uint64_t kNoSlot = ~0ull;
-constexpr int kScanItems = 8, kScanTile = 256 * kScanItems;  // entries per scan block
 
 // ---------------------------------------------------------------- load
 // One in-memory GroupAffine record (104 / 200 B: 6 LE u64 per coordinate in ark-ff Montgomery form,
@@ -331,143 +333,49 @@ __global__ void __launch_bounds__(64) k_msm_final(const uint32_t* __restrict__ p
   emit_point(out, x, y, false);
 }
 
-// ---------------------------------------------------------------- plan
-// Workspace layout for (g2, n, c). Partial sums ping-pong between two regions A and B of the
-// pool behind the n bases. A level with `in` entries has at most min(in, in / L + NB) chunks
-// (ceil(x / L) <= x, and <= x / L + 1 per non-empty bucket), so the regions are sized by
-// U1 = min(E, E / L + NB) and U2 = min(U1, U1 / L + NB) for E = n W entries, and both hold the bit
-// partials' first level, W c ceil(2^(c-1) / L) chunks.
-struct MsmPlan {
-  uint32_t c, nwin, nb, levels, ntiles;
-  uint64_t upper[8];  // upper[k]: entries of level k at most (upper[0] = n W)
-  uint64_t cap, base_a, base_b;
-  uint64_t cnt, off_a, off_b, sums, idx, pool, bytes;  // byte offsets
-  bool ok;
-};
-MsmPlan msm_plan(bool g2, uint64_t n, uint32_t c) {
-  MsmPlan p = {};
-  if (n > kMsmMaxN || c < 1 || c > kMsmWindowMax) return p;
-  p.c = c;
-  p.nwin = (256 + c - 1) / c;
-  p.nb = p.nwin << c;
-  if (n * p.nwin >= (1ull << 32)) return p;  // offsets and entry counts are 32-bit
-  p.levels = 1;
-  for (uint64_t r = L; r < n; r *= L) p.levels++;
-  p.upper[0] = n * p.nwin;
-  for (uint32_t k = 0; k < p.levels; k++) {
-    const uint64_t in = p.upper[k], by_bucket = in / L + p.nb;
-    p.upper[k + 1] = in < by_bucket ? in : by_bucket;
-  }
-  const uint64_t bits0 = (uint64_t)p.nwin * c * ((((uint64_t)1 << (c - 1)) + L - 1) / L);
-  const uint64_t u1 = p.upper[1], u2 = p.levels > 1 ? p.upper[2] : 0;
-  const uint64_t cap_a = u1 > bits0 ? u1 : bits0, cap_b = u2 > bits0 ? u2 : bits0;
-  p.base_a = n;
-  p.base_b = n + cap_a;
-  p.cap = n + cap_a + cap_b;
-  p.ntiles = (p.nb + kScanTile - 1) / kScanTile;
-  const uint64_t rows = g2 ? Geo<fp2>::ROWS : Geo<fp>::ROWS;
-  uint64_t o = 0;
-  p.cnt = o, o += align256((uint64_t)p.nb * 4);
-  p.off_a = o, o += align256((uint64_t)(p.nb + 1) * 4);
-  p.off_b = o, o += align256((uint64_t)(p.nb + 1) * 4);
-  p.sums = o, o += align256((uint64_t)(p.ntiles + 1) * 4);
-  p.idx = o, o += align256(p.upper[0] * 4);
-  p.pool = o, o += align256(p.cap * rows * 4);
-  p.bytes = o;
-  p.ok = true;
-  return p;
-}
-// NB <= 16 x 2^16 (c = 16), so one block scans the tile sums; L^6 >= 2^26, so levels <= 6 < 8
-static_assert((uint64_t)kScanTile * kScanTile >= (16u << 16), "one block scans the tile sums");
-static_assert((uint64_t)L * L * L * L * L * L >= kMsmMaxN, "upper[] holds every level of the largest n");
-
-dim3 blocks_for(uint64_t n, int b) { return dim3((unsigned)(n ? (n + b - 1) / b : 1)); }
-
+// ---------------------------------------------------------------- launch
+// The fixed prologue, then the plan's steps (plans.hpp: every region, base and lane count is the plan's)
 template <typename F>
 hipError_t launch(const MsmPlan& p, const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, bool mont,
                   void* d_work, unsigned long long* key, hipStream_t s) {
   constexpr int BLOCK = Geo<F>::BLOCK;
   uint8_t* w = (uint8_t*)d_work;
   uint32_t* cnt = (uint32_t*)(w + p.cnt);
-  uint32_t* off_cur = (uint32_t*)(w + p.off_a);
-  uint32_t* off_nxt = (uint32_t*)(w + p.off_b);
   uint32_t* sums = (uint32_t*)(w + p.sums);
   uint32_t* idx = (uint32_t*)(w + p.idx);
   uint32_t* pool = (uint32_t*)(w + p.pool);
   const uint32_t* inf = pool + (uint64_t)Geo<F>::INF_ROW * p.cap;
   const uint32_t* scalars = (const uint32_t*)d_scalars;
   const dim3 b256(256);
+  auto offsets = [&](uint64_t at) { return at == kMsmNoOffsets ? nullptr : (uint32_t*)(w + at); };
   auto scan = [&](uint32_t* off) {  // off = exclusive scan of cnt, off[nb] = total
     hipLaunchKernelGGL(k_msm_scan_tiles, dim3(p.ntiles), b256, 0, s, cnt, off, sums, p.nb, key);
     hipLaunchKernelGGL(k_msm_scan_tiles, dim3(1), b256, 0, s, sums, sums, sums + p.ntiles, p.ntiles, key);
-    hipLaunchKernelGGL(k_msm_scan_add, blocks_for(p.nb, 256), b256, 0, s, off, sums, p.nb, p.ntiles, key);
+    hipLaunchKernelGGL(k_msm_scan_add, dim3(grid_for(p.nb, 256)), b256, 0, s, off, sums, p.nb, p.ntiles, key);
   };
   if (hipError_t e = hipMemsetAsync(cnt, 0, (size_t)p.nb * 4, s)) return e;
-  hipLaunchKernelGGL(k_msm_load<F>, blocks_for(n, 256), b256, 0, s, d_bases, pool, p.cap, n, mont ? 1 : 0, key);
-  hipLaunchKernelGGL(k_msm_count, blocks_for(n, 256), b256, 0, s, scalars, inf, n, p.c, p.nwin, cnt, key);
-  scan(off_cur);
-  hipLaunchKernelGGL(k_msm_scatter, blocks_for(n, 256), b256, 0, s, scalars, inf, n, p.c, p.nwin, cnt, off_cur, idx, key);
-
-  uint64_t in_base = 0, out_base = p.base_a, other = p.base_b;
-  auto sum = [&](const SumArgs& a, uint64_t lanes) {
-    hipLaunchKernelGGL(k_msm_sum<F>, blocks_for(lanes, BLOCK), dim3(BLOCK), 0, s, pool, p.cap, a, key);
-    in_base = out_base;
-    out_base = other;
-    other = in_base;
-  };
-  for (uint32_t k = 0; k < p.levels; k++) {
-    hipLaunchKernelGGL(k_msm_chunks, blocks_for(p.nb, 256), b256, 0, s, off_cur, cnt, p.nb, key);
-    scan(off_nxt);
-    sum(SumArgs{idx, off_cur, off_nxt, in_base, out_base, k ? 1u : 0u, p.nb, p.c, 0, 0, 0}, p.upper[k + 1]);
-    uint32_t* t = off_cur;
-    off_cur = off_nxt;
-    off_nxt = t;
+  hipLaunchKernelGGL(k_msm_load<F>, dim3(grid_for(n, 256)), b256, 0, s, d_bases, pool, p.cap, n, mont ? 1 : 0, key);
+  hipLaunchKernelGGL(k_msm_count, dim3(grid_for(n, 256)), b256, 0, s, scalars, inf, n, p.c, p.nwin, cnt, key);
+  scan(offsets(p.off_a));
+  hipLaunchKernelGGL(k_msm_scatter, dim3(grid_for(n, 256)), b256, 0, s, scalars, inf, n, p.c, p.nwin, cnt,
+                     offsets(p.off_a), idx, key);
+  for (uint32_t k = 0; k < p.nsteps; k++) {
+    const MsmStep& st = p.step[k];
+    const bool buckets = st.mode < 2;
+    uint32_t *off_in = offsets(st.off_in), *off_out = offsets(st.off_out);
+    if (buckets) {
+      hipLaunchKernelGGL(k_msm_chunks, dim3(grid_for(p.nb, 256)), b256, 0, s, off_in, cnt, p.nb, key);
+      scan(off_out);
+    }
+    const SumArgs a = {buckets ? idx : nullptr, off_in, off_out, st.in_base, st.out_base, st.mode, p.nb, p.c,
+                       st.nseg, st.seg_len, st.seg_chunks};
+    hipLaunchKernelGGL(k_msm_sum<F>, dim3(grid_for(st.lanes, BLOCK)), dim3(BLOCK), 0, s, pool, p.cap, a, key);
   }
-  const uint32_t nseg = p.nwin * p.c;
-  uint32_t seg_len = 1u << (p.c - 1), mode = 2;
-  do {
-    const uint32_t chunks = (seg_len + L - 1) / L;
-    sum(SumArgs{nullptr, off_cur, nullptr, in_base, out_base, mode, p.nb, p.c, nseg, seg_len, chunks},
-        (uint64_t)nseg * chunks);
-    seg_len = chunks;
-    mode = 3;
-  } while (seg_len > 1);
-  hipLaunchKernelGGL(k_msm_final<F>, dim3(1), dim3(64), 0, s, pool, p.cap, in_base, (int)nseg, (uint4*)d_out, key);
+  hipLaunchKernelGGL(k_msm_final<F>, dim3(1), dim3(64), 0, s, pool, p.cap, p.final_base, (int)p.nseg, (uint4*)d_out, key);
   return hipGetLastError();
 }
 
 }  // namespace
-
-// Width table: c = 8 below the first threshold, one more at each threshold n reaches. The
-// thresholds are the smallest n at which the model
-//   n W + B + 43 (W max(min(n, 2^c), n / L) + B / L),   W = ceil(256 / c), B = W c 2^(c-1)
-// (bucket additions, bit-partial additions, and one inversion of about 43 additions' worth per
-// level-0 partial) prefers c to c - 1 (tests/test_msm_model.py recomputes them). Narrower windows than 8 would win the model below
-// n = 300 only, where the call is launch-bound; they are reachable by override.
-constexpr uint64_t kWidthFrom[8] = {28416, 55872, 120384, 238720, 472064, 1114113, 2244609, 3669568};  // c = 9 .. 16
-uint32_t msm_window_bits(uint64_t n) {
-  uint32_t c = 8;
-  for (uint64_t t : kWidthFrom)
-    if (n >= t) c++;
-  return c;
-}
-
-// The library's own width grows with n while the sorted-entry array (n W words) shrinks with the
-// width, so the size for "the library chooses" (c = 0) is the largest over the widths 8 .. c(n):
-// every term is monotone in n for a fixed width, hence so is this maximum.
-uint64_t msm_workspace_bytes(bool g2, uint64_t n, uint32_t c) {
-  if (c) {
-    const MsmPlan p = msm_plan(g2, n, c);
-    return p.ok ? p.bytes : 0;
-  }
-  uint64_t bytes = 0;
-  for (uint32_t w = 8; w <= msm_window_bits(n); w++) {
-    const MsmPlan p = msm_plan(g2, n, w);
-    if (!p.ok) return 0;
-    if (p.bytes > bytes) bytes = p.bytes;
-  }
-  return bytes;
-}
 
 hipError_t launch_msm(bool g2, const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, bool mont,
                       uint32_t c, void* d_work, unsigned long long* d_key, hipStream_t stream) {

@@ -10,9 +10,7 @@ using namespace kzgpot;
 
 namespace {
 
-constexpr uint32_t kTileFlags = KZGPOT_POLY_TILE(0xf);
-constexpr uint32_t kOpenFlags = kTileFlags | KZGPOT_MSM_BASES_MONT | KZGPOT_MSM_WINDOW(0x1f);
-constexpr uint64_t kOutBytes = 160, kPointBytes = 96;
+constexpr uint64_t kPointBytes = point_record(false), kOutBytes = kPointBytes + 64;
 
 // z^(2^k) for k < kPolyPowers; z is any 256-bit integer
 fr_powers<kPolyPowers> z_powers(const uint8_t z_le32[32]) {
@@ -25,8 +23,7 @@ fr_powers<kPolyPowers> z_powers(const uint8_t z_le32[32]) {
 int poly_divide_dev(const void* d_coeffs, uint64_t n, const uint8_t* z, void* d_quotient, void* d_value, uint32_t flags,
                     void* d_work, void* stream) {
   uint32_t t;
-  if ((flags & ~kTileFlags) || !poly_tile_flag(flags, t) || !poly_workspace_bytes(n, t) || !z || !d_value || !d_work ||
-      (n && !d_coeffs))
+  if (!poly_flags(flags, t) || !poly_workspace_bytes(n, t) || !z || !d_value || !d_work || (n && !d_coeffs))
     return KZGPOT_E_INVALID_ARG;
   const fr_powers<kPolyPowers> zp = z_powers(z);
   HIP_TRY(launch_poly_divide(d_coeffs, n, zp, d_quotient, d_value, t, d_work, (hipStream_t)stream));
@@ -36,7 +33,7 @@ int poly_divide_dev(const void* d_coeffs, uint64_t n, const uint8_t* z, void* d_
 int poly_divide_host(const uint8_t* coeffs, uint64_t n, const uint8_t* z, uint8_t* quotient, uint8_t* value,
                      uint32_t flags) {
   uint32_t t;
-  const uint64_t work_bytes = !(flags & ~kTileFlags) && poly_tile_flag(flags, t) ? poly_workspace_bytes(n, t) : 0;
+  const uint64_t work_bytes = poly_flags(flags, t) ? poly_workspace_bytes(n, t) : 0;
   if (!work_bytes || !z || !value || (n && !coeffs)) return KZGPOT_E_INVALID_ARG;
   if (device_count() <= 0) return KZGPOT_E_DEVICE;
   DeviceGuard guard;
@@ -54,33 +51,7 @@ int poly_divide_host(const uint8_t* coeffs, uint64_t n, const uint8_t* z, uint8_
 }
 
 // ---------------------------------------------------------------- open
-// Workspace: the two base ranges end to end (what the one MSM reads), the two quotients end to
-// end (its scalars), the two evaluations, the division's levels, the MSM's own workspace.
-struct OpenPlan {
-  uint32_t t, c;  // c: the width override, 0 for the library's
-  uint64_t nq, nb, rec;
-  uint64_t bases, scalars, values, poly, msm, bytes;  // byte offsets
-  bool ok;
-};
-OpenPlan open_plan(uint64_t n, uint64_t n_blind, uint32_t flags) {
-  OpenPlan p = {};
-  if ((flags & ~kOpenFlags) || !poly_tile_flag(flags, p.t) || n > kPolyMaxN || n_blind > kPolyMaxN) return p;
-  p.nq = n ? n - 1 : 0;
-  p.nb = n_blind ? n_blind - 1 : 0;
-  p.rec = (flags & KZGPOT_MSM_BASES_MONT) ? KZGPOT_G1_ARK_MONT_BYTES : kPointBytes;
-  const uint64_t msm_bytes = msm_window_flag(flags, p.c) ? msm_workspace_bytes(false, p.nq + p.nb, p.c) : 0;
-  if (!msm_bytes) return p;
-  uint64_t o = 0;
-  p.bases = o, o += align256((p.nq + p.nb) * p.rec);
-  p.scalars = o, o += align256((p.nq + p.nb) * 32);
-  p.values = o, o += 256;
-  p.poly = o, o += poly_workspace_bytes(n > n_blind ? n : n_blind, p.t);  // one division at a time
-  p.msm = o, o += msm_bytes;
-  p.bytes = o;
-  p.ok = true;
-  return p;
-}
-
+// The workspace is open_plan's (plans.hpp).
 // host_key (optional): receives the bad key once the proof is done
 int open_dev(const void* d_powers_of_g, const void* d_coeffs, uint64_t n, const void* d_powers_of_gamma_g,
              const void* d_blinding, uint64_t n_blind, const uint8_t* z, void* d_out, uint32_t flags, void* d_work,
@@ -144,7 +115,7 @@ extern "C" {
 /* host only */
 uint64_t kzgpot_fr_poly_workspace(uint64_t n, uint32_t flags) {
   uint32_t t;
-  return !(flags & ~kTileFlags) && poly_tile_flag(flags, t) ? poly_workspace_bytes(n, t) : 0;
+  return poly_flags(flags, t) ? poly_workspace_bytes(n, t) : 0;
 }
 uint64_t kzgpot_kzg_open_workspace(uint64_t n, uint64_t n_blind, uint32_t flags) {
   return open_plan(n, n_blind, flags).bytes;

@@ -1,0 +1,292 @@
+// The launch plans of the group FFT (fft_kernels.hip), the multi-scalar multiplication
+// (msm_kernels.hip), the polynomial division (poly_kernels.hip) and KZG10 open (open.hip), each stated
+// once: where every kernel reads and writes inside the caller-supplied workspace, and the launch
+// schedule as data (one entry per stage, level or step, in launch order). The launchers run the
+// tables; nothing else decides an offset or a lane count.
+//
+// Plain C++17 with no HIP header, so a host program can include this file alone
+// (tests/host_units/plan_units.cpp, built by g++ with and without sanitizers; tests/test_plan_units.py
+// checks every launch's reads and writes against its regions).
+#pragma once
+#include <stdint.h>
+
+#include "../../include/kzgpot.h"
+
+namespace kzgpot {
+
+constexpr uint64_t align256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }  // every workspace region's size
+// blocks of `block` lanes for n items; one block (whose lanes all leave) for none
+inline unsigned grid_for(uint64_t n, uint32_t block) { return (unsigned)(n ? (n + block - 1) / block : 1); }
+
+// ---------------------------------------------------------------- records and work rows
+// rows of a work-row point (group_parts.hpp): x and y of NW = 14 (G1) or 28 (G2) words, the infinity mark
+constexpr uint32_t kWorkRowsG1 = 2 * 14 + 1, kWorkRowsG2 = 2 * 28 + 1;
+constexpr uint64_t work_rows(bool g2) { return g2 ? kWorkRowsG2 : kWorkRowsG1; }
+// one ark-uncompressed point, and one base of an MSM: that, or (mont) the loaders' in-memory GroupAffine
+constexpr uint64_t point_record(bool g2) { return g2 ? 192 : 96; }
+constexpr uint64_t base_record(bool g2, bool mont) {
+  return !mont ? point_record(g2) : g2 ? KZGPOT_G2_ARK_MONT_BYTES : KZGPOT_G1_ARK_MONT_BYTES;
+}
+
+// ---------------------------------------------------------------- group FFT
+// d_work: the twiddle table (m/2 + 1 scalars of 32 B: w^(+-j) for j < m/2, then 1/m), then the work
+// rows of m points. Stage st has half-block h = 2^logh = 2^st and nb = 2^lognb = m / 2h blocks; the
+// uniform instantiation runs where the nb butterflies that share a twiddle fill whole waves.
+constexpr uint32_t kFftMaxExp = 32;
+struct FftStage {
+  uint32_t lognb, logh;
+  bool uniform;
+};
+struct FftPlan {
+  uint64_t m, half;            // points; butterflies per stage
+  uint64_t work, bytes;        // byte offset of the work rows (= the twiddle table's size); the total
+  uint32_t nstages;
+  FftStage stage[kFftMaxExp];
+  bool scale;                  // the inverse's pass [1/m] over all m points (1/m = 1 at m = 1)
+  bool ok;
+};
+inline FftPlan fft_plan(bool g2, uint32_t exp, bool inverse) {
+  FftPlan p = {};
+  if (exp > kFftMaxExp) return p;
+  p.m = (uint64_t)1 << exp;
+  p.half = p.m >> 1;
+  p.work = align256((p.half + 1) * 32);
+  p.bytes = p.work + p.m * work_rows(g2) * 4;
+  p.nstages = exp;
+  for (uint32_t st = 0; st < exp; st++) {
+    const uint32_t lognb = exp - 1 - st;
+    p.stage[st] = FftStage{lognb, st, lognb >= 6};
+  }
+  p.scale = inverse && exp > 0;
+  p.ok = true;
+  return p;
+}
+inline uint64_t fft_twiddle_bytes(uint32_t exp) { return fft_plan(false, exp, false).work; }
+inline uint64_t fft_workspace_bytes(bool g2, uint32_t exp) { return fft_plan(g2, exp, false).bytes; }
+
+// ---------------------------------------------------------------- multi-scalar multiplication
+constexpr uint32_t kMsmChunk = 64;  // L: no lane sums more entries than this
+constexpr uint64_t kMsmMaxN = 1ull << 26;
+constexpr uint32_t kMsmWindowMax = 16;
+constexpr uint32_t kMsmFlags = KZGPOT_MSM_BASES_MONT | KZGPOT_MSM_WINDOW(0x1f);
+// KZGPOT_MSM_WINDOW(c) in the flags: c = 0 (the library chooses) or the width; false: above kMsmWindowMax
+inline bool msm_window_flag(uint32_t flags, uint32_t& c) {
+  c = (flags >> 8) & 0x1fu;
+  return c <= kMsmWindowMax;
+}
+// the MSM's flags; false: an unknown bit or an invalid width
+inline bool msm_flags(uint32_t flags, uint32_t& c) { return msm_window_flag(flags, c) && !(flags & ~kMsmFlags); }
+
+// the exclusive scan of the NB bucket counts: tiles of kScanTile entries, then one block over the tile sums
+constexpr int kScanItems = 8, kScanTile = 256 * kScanItems;
+// bucket levels: L^levels >= n; bit-partial levels: 2^(c-1) entries per segment in chunks of L down to one
+constexpr uint32_t kMsmMaxLevels = 6, kMsmMaxBitLevels = 3, kMsmMaxSteps = kMsmMaxLevels + kMsmMaxBitLevels;
+constexpr uint64_t kMsmNoOffsets = ~0ull;  // MsmStep::off_out of a step that writes no chunk offsets
+static_assert((uint64_t)kScanTile * kScanTile >= ((uint64_t)kMsmWindowMax << kMsmWindowMax),
+              "NB <= 16 x 2^16 (c = 16): one block scans the tile sums");
+static_assert((uint64_t)kMsmChunk * kMsmChunk * kMsmChunk * kMsmChunk * kMsmChunk * kMsmChunk >= kMsmMaxN,
+              "step[] holds every bucket level of the largest n");
+static_assert((1ull << (kMsmWindowMax - 1)) <= (uint64_t)kMsmChunk * kMsmChunk * kMsmChunk,
+              "step[] holds every bit-partial level of the widest window");
+
+// One k_msm_sum launch (msm_kernels.hip documents the modes). `lanes` lanes write the pool slots
+// [out_base, out_base + lanes); they read below in_base + (the previous step's lanes), or for mode 0
+// the n bases through idx. Modes 0, 1 (a bucket level): k_msm_chunks and the scan turn the entry
+// offsets off_in into the chunk offsets off_out first. Modes 2, 3 (a bit-partial level): nseg
+// segments of seg_len entries in seg_chunks chunks; mode 2 finds its entries through off_in.
+struct MsmStep {
+  uint32_t mode, nseg, seg_len, seg_chunks;
+  uint64_t in_base, out_base, lanes;  // pool slots
+  uint64_t off_in, off_out;           // byte offsets of the two offset arrays, or kMsmNoOffsets
+};
+// Workspace layout and schedule for (g2, n, c): W = ceil(256 / c) windows, NB = W 2^c buckets.
+// Partial sums ping-pong between two regions A and B of the pool behind the n bases, the offsets
+// between the arrays off_a and off_b. A level with `in` entries has at most min(in, in / L + NB)
+// chunks (ceil(x / L) <= x, and <= x / L + 1 per non-empty bucket), so the regions are sized by
+// U1 = min(E, E / L + NB) and U2 = min(U1, U1 / L + NB) for E = n W entries, and both hold the bit
+// partials' first level, W c ceil(2^(c-1) / L) chunks.
+struct MsmPlan {
+  uint32_t c, nwin, nb, levels, ntiles;  // levels: the bucket levels, steps [0, levels)
+  uint32_t nseg;                         // W c bit partials
+  uint64_t entries;                      // n W: the sorted point indices
+  uint64_t cap, base_a, base_b;          // pool slots: the total, and where A and B start
+  uint64_t cnt, off_a, off_b, sums, idx, pool, bytes;  // byte offsets
+  uint32_t nsteps;
+  MsmStep step[kMsmMaxSteps];
+  uint64_t final_base;  // k_msm_final reads the nseg slots from here
+  bool ok;
+};
+inline MsmPlan msm_plan(bool g2, uint64_t n, uint32_t c) {
+  constexpr uint64_t L = kMsmChunk;
+  MsmPlan p = {};
+  if (n > kMsmMaxN || c < 1 || c > kMsmWindowMax) return p;
+  p.c = c;
+  p.nwin = (256 + c - 1) / c;
+  p.nb = p.nwin << c;
+  p.nseg = p.nwin * c;
+  p.entries = n * p.nwin;
+  if (p.entries >= (1ull << 32)) return p;  // offsets and entry counts are 32-bit
+  p.levels = 1;
+  for (uint64_t r = L; r < n; r *= L) p.levels++;
+  uint64_t upper[kMsmMaxLevels + 1] = {p.entries};  // upper[k]: entries of level k at most
+  for (uint32_t k = 0; k < p.levels; k++) {
+    const uint64_t in = upper[k], by_bucket = in / L + p.nb;
+    upper[k + 1] = in < by_bucket ? in : by_bucket;
+  }
+  const uint64_t bits0 = (uint64_t)p.nseg * ((((uint64_t)1 << (c - 1)) + L - 1) / L);
+  const uint64_t u1 = upper[1], u2 = p.levels > 1 ? upper[2] : 0;
+  const uint64_t cap_a = u1 > bits0 ? u1 : bits0, cap_b = u2 > bits0 ? u2 : bits0;
+  p.base_a = n;
+  p.base_b = n + cap_a;
+  p.cap = n + cap_a + cap_b;
+  p.ntiles = (p.nb + kScanTile - 1) / kScanTile;
+  uint64_t o = 0;
+  p.cnt = o, o += align256((uint64_t)p.nb * 4);
+  p.off_a = o, o += align256((uint64_t)(p.nb + 1) * 4);
+  p.off_b = o, o += align256((uint64_t)(p.nb + 1) * 4);
+  p.sums = o, o += align256((uint64_t)(p.ntiles + 1) * 4);
+  p.idx = o, o += align256(p.entries * 4);
+  p.pool = o, o += align256(p.cap * work_rows(g2) * 4);
+  p.bytes = o;
+
+  uint64_t in_base = 0, out_base = p.base_a;  // level 0 reads the bases and writes A
+  uint64_t off_in = p.off_a, off_out = p.off_b;
+  auto push = [&](MsmStep s) {
+    s.in_base = in_base, s.out_base = out_base;
+    p.step[p.nsteps++] = s;
+    in_base = out_base;
+    out_base = in_base == p.base_a ? p.base_b : p.base_a;
+  };
+  for (uint32_t k = 0; k < p.levels; k++) {
+    push(MsmStep{k ? 1u : 0u, 0, 0, 0, 0, 0, upper[k + 1], off_in, off_out});
+    const uint64_t t = off_in;
+    off_in = off_out;
+    off_out = t;
+  }
+  uint32_t seg_len = 1u << (c - 1), mode = 2;
+  do {
+    const uint32_t chunks = (seg_len + kMsmChunk - 1) / kMsmChunk;
+    push(MsmStep{mode, p.nseg, seg_len, chunks, 0, 0, (uint64_t)p.nseg * chunks, off_in, kMsmNoOffsets});
+    seg_len = chunks;
+    mode = 3;
+  } while (seg_len > 1);
+  p.final_base = in_base;
+  p.ok = true;
+  return p;
+}
+
+// Width table: c = 8 below the first threshold, one more at each threshold n reaches. The
+// thresholds are the smallest n at which the model
+//   n W + B + 43 (W max(min(n, 2^c), n / L) + B / L),   W = ceil(256 / c), B = W c 2^(c-1)
+// (bucket additions, bit-partial additions, and one inversion of about 43 additions' worth per
+// level-0 partial) prefers c to c - 1 (tests/test_msm_model.py recomputes them). Narrower windows
+// than 8 would win the model below n = 300 only, where the call is launch-bound; they are reachable
+// by override.
+constexpr uint64_t kWidthFrom[8] = {28416, 55872, 120384, 238720, 472064, 1114113, 2244609, 3669568};  // c = 9 .. 16
+inline uint32_t msm_window_bits(uint64_t n) {
+  uint32_t c = 8;
+  for (uint64_t t : kWidthFrom)
+    if (n >= t) c++;
+  return c;
+}
+// 0 where (n, c) is not supported. c = 0: "the library's choice, msm_window_bits(n)". That width
+// grows with n while the sorted-entry array (n W words) shrinks with the width, so the size for
+// c = 0 is the largest over the widths 8 .. c(n): every term is monotone in n for a fixed width,
+// hence so is this maximum.
+inline uint64_t msm_workspace_bytes(bool g2, uint64_t n, uint32_t c) {
+  if (c) return msm_plan(g2, n, c).bytes;  // 0 unless ok
+  uint64_t bytes = 0;
+  for (uint32_t w = 8; w <= msm_window_bits(n); w++) {
+    const MsmPlan p = msm_plan(g2, n, w);
+    if (!p.ok) return 0;
+    if (p.bytes > bytes) bytes = p.bytes;
+  }
+  return bytes;
+}
+
+// ---------------------------------------------------------------- polynomial division
+// t: tile width 2^t, kPolyTileMin .. kPolyTileMax. z_pow.p[k] = z^(2^k), kPolyPowers entries.
+constexpr uint32_t kPolyTileMin = 8, kPolyTileMax = 12, kPolyTile = 11;
+constexpr uint64_t kPolyMaxN = (1ull << 26) + 1;
+constexpr int kPolyPowers = 64;
+constexpr uint32_t kPolyMaxLevels = 4;
+constexpr uint32_t kPolyFlags = KZGPOT_POLY_TILE(0xf);
+// KZGPOT_POLY_TILE(t) in the flags: t, or the library's for 0; false: outside kPolyTileMin .. kPolyTileMax
+inline bool poly_tile_flag(uint32_t flags, uint32_t& t) {
+  t = (flags >> 16) & 0xfu;
+  if (!t) t = kPolyTile;
+  return t >= kPolyTileMin && t <= kPolyTileMax;
+}
+// the division's flags; false: an unknown bit or an invalid tile
+inline bool poly_flags(uint32_t flags, uint32_t& t) { return poly_tile_flag(flags, t) && !(flags & ~kPolyFlags); }
+
+// 2^26 + 1 entries in tiles of 2^8 leave 5 at level 3, and level k's multiplier is z^(S^k), whose
+// powers y^(2^j), j < kPolyTileMax, are z_pow's entries k t + j
+static_assert(((kPolyMaxN - 1) >> (3 * kPolyTileMin)) + 1 <= (1u << kPolyTileMin), "at most kPolyMaxLevels levels");
+static_assert((kPolyMaxLevels - 1) * kPolyTileMax + kPolyTileMax <= (uint32_t)kPolyPowers,
+              "z_pow holds the top level's powers");
+
+// Level k has cnt entries of 32 B in `tiles` tiles; level 0 is the caller's array (off unused),
+// levels 1 .. top live in the workspace at byte offset off, one entry per tile of the level below.
+struct PolyLevel {
+  uint64_t cnt, off, tiles;
+  uint32_t pow0;  // the level reads z_pow.p[pow0 .. pow0 + kPolyTileMax)
+};
+struct PolyPlan {
+  uint32_t top;
+  PolyLevel level[kPolyMaxLevels];
+  uint64_t bytes;  // 0: invalid arguments
+};
+inline PolyPlan poly_plan(uint64_t n, uint32_t t) {
+  PolyPlan p = {};
+  if (n > kPolyMaxN || t < kPolyTileMin || t > kPolyTileMax) return p;
+  for (uint64_t cnt = n;; p.top++) {
+    PolyLevel& l = p.level[p.top];
+    l.cnt = cnt;
+    l.tiles = (cnt + ((uint64_t)1 << t) - 1) >> t;
+    l.pow0 = p.top * t;
+    if (p.top) {
+      l.off = p.bytes;
+      p.bytes += align256(cnt * 32);
+    }
+    if (l.tiles <= 1) break;
+    cnt = l.tiles;
+  }
+  if (!p.bytes) p.bytes = 256;  // a size of 0 means invalid arguments
+  return p;
+}
+inline uint64_t poly_workspace_bytes(uint64_t n, uint32_t t) { return poly_plan(n, t).bytes; }
+
+// ---------------------------------------------------------------- KZG10 open
+// Workspace: the two base ranges end to end (what the one MSM reads), the two quotients end to
+// end (its scalars), the two evaluations, the division's levels, the MSM's own workspace.
+constexpr uint32_t kOpenFlags = kPolyFlags | kMsmFlags;
+inline bool open_flags(uint32_t flags, uint32_t& t, uint32_t& c) {
+  return poly_tile_flag(flags, t) && msm_window_flag(flags, c) && !(flags & ~kOpenFlags);
+}
+struct OpenPlan {
+  uint32_t t, c;  // c: the width override, 0 for the library's
+  uint64_t nq, nb, rec;
+  uint64_t bases, scalars, values, poly, msm, bytes;  // byte offsets
+  bool ok;
+};
+inline OpenPlan open_plan(uint64_t n, uint64_t n_blind, uint32_t flags) {
+  OpenPlan p = {};
+  if (!open_flags(flags, p.t, p.c) || n > kPolyMaxN || n_blind > kPolyMaxN) return p;
+  p.nq = n ? n - 1 : 0;
+  p.nb = n_blind ? n_blind - 1 : 0;
+  p.rec = base_record(false, flags & KZGPOT_MSM_BASES_MONT);
+  const uint64_t msm_bytes = msm_workspace_bytes(false, p.nq + p.nb, p.c);
+  if (!msm_bytes) return p;
+  uint64_t o = 0;
+  p.bases = o, o += align256((p.nq + p.nb) * p.rec);
+  p.scalars = o, o += align256((p.nq + p.nb) * 32);
+  p.values = o, o += 256;
+  p.poly = o, o += poly_workspace_bytes(n > n_blind ? n : n_blind, p.t);  // one division at a time
+  p.msm = o, o += msm_bytes;
+  p.bytes = o;
+  p.ok = true;
+  return p;
+}
+
+}  // namespace kzgpot

@@ -29,6 +29,9 @@
 // the up pass, reads them again and writes 32 B in the down pass: 96 B per coefficient; the upper
 // levels add 96 / S of that.
 //
+// The levels (entry counts, tiles, workspace offsets, which powers of z each reads) are poly_plan's
+// (plans.hpp, checked on the CPU by tests/test_plan_units.py).
+//
 // Values are Montgomery (R = 2^256) between load and store: coefficients are 256-bit integers
 // reduced on the way in (fr_load, csrc/fr.hpp), the quotient and the value leave canonical.
 #include <hip/hip_runtime.h>
@@ -215,44 +218,24 @@ __global__ void __launch_bounds__(64) k_open_emit(const uint32_t* __restrict__ v
   if (threadIdx.x < 16) out[threadIdx.x] = values[threadIdx.x];
 }
 
-// Level k has cnt[k] entries; level 0 is the caller's array, levels 1 .. top live in the workspace.
-struct PolyPlan {
-  uint32_t top;
-  uint64_t cnt[8], off[8], bytes;
-};
-PolyPlan poly_plan(uint64_t n, uint32_t t) {
-  PolyPlan p = {};
-  p.cnt[0] = n;
-  while (p.cnt[p.top] > ((uint64_t)1 << t)) {
-    p.cnt[p.top + 1] = (p.cnt[p.top] + ((uint64_t)1 << t) - 1) >> t;
-    p.top++;
-    p.off[p.top] = p.bytes;
-    p.bytes += align256(p.cnt[p.top] * 32);
-  }
-  if (!p.bytes) p.bytes = 256;  // a size of 0 means invalid arguments
-  return p;
-}
-// 2^26 + 1 entries in tiles of 2^8 leave 5 at level 3: cnt[] and the power table hold every level
-static_assert(((kPolyMaxN - 1) >> (3 * kPolyTileMin)) + 1 <= (1u << kPolyTileMin), "at most 4 levels");
-static_assert(3 * kPolyTileMax + kPolyTileMax <= kPolyPowers, "z_pow holds the top level's powers");
-
+// The up passes, then the down passes from the top: the levels are poly_plan's (plans.hpp)
 template <int T>
 hipError_t launch(const PolyPlan& p, const void* d_coeffs, const fr_powers<kPolyPowers>& z_pow, void* d_quotient,
                   void* d_value, void* d_work, hipStream_t s) {
   uint8_t* w = (uint8_t*)d_work;
-  auto level = [&](uint32_t k) -> void* { return k ? (void*)(w + p.off[k]) : const_cast<void*>(d_coeffs); };
+  auto level = [&](uint32_t k) -> void* { return k ? (void*)(w + p.level[k].off) : const_cast<void*>(d_coeffs); };
   auto powers = [&](uint32_t k) {
     PolyPowers pw;
-    for (uint32_t j = 0; j < kPolyTileMax; j++) pw.p[j] = z_pow.p[k * T + j];
+    for (uint32_t j = 0; j < kPolyTileMax; j++) pw.p[j] = z_pow.p[p.level[k].pow0 + j];
     return pw;
   };
-  auto tiles = [&](uint32_t k) { return dim3((unsigned)((p.cnt[k] + (1u << T) - 1) >> T)); };
+  auto tiles = [&](uint32_t k) { return dim3((unsigned)p.level[k].tiles); };
   for (uint32_t k = 0; k < p.top; k++)
-    hipLaunchKernelGGL(k_poly_up<T>, tiles(k), dim3(256), 0, s, (const uint4*)level(k), p.cnt[k], k == 0 ? 1 : 0,
+    hipLaunchKernelGGL(k_poly_up<T>, tiles(k), dim3(256), 0, s, (const uint4*)level(k), p.level[k].cnt, k == 0 ? 1 : 0,
                        (uint32_t*)level(k + 1), powers(k));
   for (uint32_t k = p.top + 1; k-- > 0;) {
     const bool last = k == 0 || !d_quotient;  // evaluate only: the top level has the value
-    hipLaunchKernelGGL(k_poly_down<T>, tiles(k), dim3(256), 0, s, (const uint4*)level(k), p.cnt[k], k == 0 ? 1 : 0,
+    hipLaunchKernelGGL(k_poly_down<T>, tiles(k), dim3(256), 0, s, (const uint4*)level(k), p.level[k].cnt, k == 0 ? 1 : 0,
                        k < p.top ? (const uint32_t*)level(k + 1) : nullptr,
                        (uint4*)(k ? (d_quotient ? level(k) : nullptr) : d_quotient), last ? (uint32_t*)d_value : nullptr,
                        powers(k));
@@ -263,16 +246,11 @@ hipError_t launch(const PolyPlan& p, const void* d_coeffs, const fr_powers<kPoly
 
 }  // namespace
 
-uint64_t poly_workspace_bytes(uint64_t n, uint32_t t) {
-  if (n > kPolyMaxN || t < kPolyTileMin || t > kPolyTileMax) return 0;
-  return poly_plan(n, t).bytes;
-}
-
 hipError_t launch_poly_divide(const void* d_coeffs, uint64_t n, const fr_powers<kPolyPowers>& z_pow, void* d_quotient,
                               void* d_value, uint32_t t, void* d_work, hipStream_t stream) {
-  if (!poly_workspace_bytes(n, t)) return hipErrorInvalidValue;
-  if (n == 0) return hipMemsetAsync(d_value, 0, 32, stream);  // the zero polynomial
   const PolyPlan p = poly_plan(n, t);
+  if (!p.bytes) return hipErrorInvalidValue;
+  if (n == 0) return hipMemsetAsync(d_value, 0, 32, stream);  // the zero polynomial
   switch (t) {
     case 8: return launch<8>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);
     case 9: return launch<9>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);

@@ -14,7 +14,7 @@ import random
 import pytest
 
 R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
-L = 64  # csrc/codec.hpp kMsmChunk
+L = 64  # csrc/plans.hpp kMsmChunk
 MAX_N = 1 << 26
 
 
@@ -26,8 +26,10 @@ def exscan(cnt):
     return off + [run]
 
 
-def msm_model(ks, scalars, c):
-    """-> (sum_i s_i k_i mod r as the schedule computes it, the most entries one lane summed)."""
+def msm_model(ks, scalars, c, level_outputs=None):
+    """-> (sum_i s_i k_i mod r as the schedule computes it, the most entries one lane summed).
+    level_outputs (a list, optional) receives the number of partial sums each bucket level wrote
+    (tests/test_plan_units.py holds them against the lane counts of the C++ plan)."""
     n, nwin, mask = len(ks), -(-256 // c), (1 << c) - 1
     nb = nwin << c
     buckets = [(i, (j << c) | ((s >> (j * c)) & mask)) for i, s in enumerate(scalars) for j in range(nwin)
@@ -58,6 +60,8 @@ def msm_model(ks, scalars, c):
             out.append(sum(entries[start:end]) % R)
         # the regions are sized by min(in, in / L + NB)
         assert len(out) <= min(len(entries), len(entries) // L + nb)
+        if level_outputs is not None:
+            level_outputs.append(len(out))
         entries, off = out, off_out
     assert all(off[b + 1] - off[b] <= 1 for b in range(nb))
     # bit partials: segment (j, bit) lists the buckets (j, d) with that bit of d set, entry e <-> d
