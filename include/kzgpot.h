@@ -350,6 +350,70 @@ int kzgpot_g1_kzg_open(const uint8_t* powers_of_g, const uint8_t* coeffs, uint64
                        const uint8_t* blinding, uint64_t n_blind, const uint8_t z_le32[32], uint8_t out[160],
                        uint32_t flags, int64_t* first_bad);
 
+/* ---------------------------------------------------------------- Fr NTT, amortized KZG10 openings (FK20) */
+/* The number-theoretic transform over Fr on the domain of size m = 2^exp generated by
+ * w = 7^((r-1)/m) (kzgpot_fr_domain_root), natural order in and out:
+ *   forward               out[i] = sum_j in[j] w^(ij)          (coefficients -> evaluations p(w^i))
+ *   KZGPOT_NTT_INVERSE    out[i] = 1/m sum_j in[j] w^(-ij)
+ * in, out: 2^exp values of 32 little-endian bytes; inputs are any 256-bit integers, each reduced mod r,
+ * outputs are canonical (below r). out may be in.
+ *   KZGPOT_POLY_TILE(t): elements per 256-lane block, 2^t with 8 <= t <= 11 (the 64 KB of LDS), in the
+ *     division's flag bits; 0: the library's tile (2^9). The result does not depend on it.
+ * exp > 26, an unknown flag bit, a tile outside 8..11 or a NULL pointer is KZGPOT_E_INVALID_ARG
+ * before any device use. */
+#define KZGPOT_NTT_INVERSE 0x1u
+/* Host only. Bytes of d_work for these arguments (at least 512); 0 when they are invalid. Two
+ * twiddle tables of about 2^(exp/2) elements each and, where the transform takes more than one pass
+ * (exp > t, t the tile), 32 x 2^exp bytes that only an in-place call uses. */
+uint64_t kzgpot_fr_ntt_workspace(uint32_t exp, uint32_t flags);
+/* Asynchronous on `stream`: d_in, d_out (16-byte aligned) and d_work in HBM. */
+int kzgpot_fr_ntt_dev(const void* d_in, uint32_t exp, void* d_out, uint32_t flags, void* d_work, void* stream);
+/* The same on host buffers, synchronous, on the current device. */
+int kzgpot_fr_ntt(const uint8_t* in, uint32_t exp, uint8_t* out, uint32_t flags);
+
+/* All n = 2^exp opening proofs of one polynomial p over the domain {w^i} at once (Feist and
+ * Khovratovich's amortized KZG proofs, "FK20"), from a table that depends on the setup and exp only:
+ *   table    T[i] = sum_{j<n} [x^(n-1-j)] powers[j], x = w_2n^i, i < 2n: the forward group FFT of size
+ *            2n over powers[n-1], .., powers[0] followed by n points at infinity. 2n ark-uncompressed
+ *            records (96 B in G1, 192 B in G2); powers: the first n records of powers_of_g (G1) or
+ *            powers_of_h (G2, the fastkzg setup), ark-uncompressed.
+ *   proofs   proofs[i] = [(p(tau) - p(w^i)) / (tau - w^i)] G, i < n, natural order: what KZG10::open
+ *            returns as w at z = w^i, without hiding. n ark-uncompressed records.
+ *   values   values[i] = p(w^i), n x 32 little-endian bytes, canonical. May be NULL: proofs only.
+ *   coeffs   n_coeffs <= n values of 32 bytes, as for the division (reduced mod r, used as given).
+ *   flags    KZGPOT_POLY_TILE(t) only, handed to the NTT.
+ * One call is two NTTs, 2n scalar multiplications, a group FFT of 2n and one of n points
+ * (O(n log n) group operations against the n multi-scalar multiplications of n openings); everything
+ * between the table and the proofs stays in HBM. Records of powers and table are checked as the group
+ * FFT checks its input: -3 / -6 with the smallest index, and a rejected call writes nothing.
+ * n_coeffs <= 1 gives n infinity records and values all c[0] mod r (0 for none). exp > 24,
+ * n_coeffs > 2^exp, an unknown flag bit, a tile outside 8..11 or a NULL pointer where a count is
+ * non-zero is KZGPOT_E_INVALID_ARG before any device use; the workspace functions then return 0.
+ * Hiding proofs are out of scope: they would need a second table over powers_of_gamma_g and the
+ * blinding polynomial. */
+/* Host only: bytes of d_work; monotone in exp. */
+uint64_t kzgpot_open_domain_table_workspace(int g2, uint32_t exp);
+uint64_t kzgpot_open_domain_workspace(int g2, uint32_t exp, uint32_t flags);
+/* Asynchronous on `stream`: every d_ pointer in HBM and 16-byte aligned, d_bad_key as for
+ * kzgpot_g1_fft_dev (an index along powers, or along table). */
+int kzgpot_g1_open_domain_table_dev(const void* d_powers, uint32_t exp, void* d_table, void* d_work,
+                                    uint64_t* d_bad_key, void* stream);
+int kzgpot_g2_open_domain_table_dev(const void* d_powers, uint32_t exp, void* d_table, void* d_work,
+                                    uint64_t* d_bad_key, void* stream);
+int kzgpot_g1_open_domain_dev(const void* d_table, const void* d_coeffs, uint64_t n_coeffs, uint32_t exp,
+                              void* d_proofs, void* d_values, uint32_t flags, void* d_work, uint64_t* d_bad_key,
+                              void* stream);
+int kzgpot_g2_open_domain_dev(const void* d_table, const void* d_coeffs, uint64_t n_coeffs, uint32_t exp,
+                              void* d_proofs, void* d_values, uint32_t flags, void* d_work, uint64_t* d_bad_key,
+                              void* stream);
+/* The same on host buffers, synchronous, on the current device. */
+int kzgpot_g1_open_domain_table(const uint8_t* powers, uint32_t exp, uint8_t* table, int64_t* first_bad);
+int kzgpot_g2_open_domain_table(const uint8_t* powers, uint32_t exp, uint8_t* table, int64_t* first_bad);
+int kzgpot_g1_open_domain(const uint8_t* table, const uint8_t* coeffs, uint64_t n_coeffs, uint32_t exp,
+                          uint8_t* proofs, uint8_t* values, uint32_t flags, int64_t* first_bad);
+int kzgpot_g2_open_domain(const uint8_t* table, const uint8_t* coeffs, uint64_t n_coeffs, uint32_t exp,
+                          uint8_t* proofs, uint8_t* values, uint32_t flags, int64_t* first_bad);
+
 /* ---------------------------------------------------------------- BN254 (config 5, next-row §8f 4) */
 /* No reference counterpart: the same path instantiated for ark-bn254 0.2 G1 (cofactor 1).
  * ark compressed (32 B: x LE, SWFlags bit7 PositiveY / bit6 Infinity in byte 31) → ark

@@ -81,6 +81,18 @@ struct FftScalars {
   fr one;     // Montgomery 1
   fr minv;    // 1/m, canonical
 };
+// The scalars of one transform of size m = 2^exp <= 2^32: the powers w^(+-2^k) (the inverse uses
+// w^-1 = w^(m-1)) and 1/m
+inline fr fft_root(uint32_t exp, bool inverse) {
+  const uint64_t m = (uint64_t)1 << exp;
+  const fr w = fr_domain_root(exp);
+  return inverse ? fr_pow(w, fr{{(uint32_t)(m - 1), 0, 0, 0, 0, 0, 0, 0}}) : w;  // m - 1 < 2^32
+}
+inline void fft_scalars(uint32_t exp, bool inverse, FftScalars& sc) {
+  fr_fill_powers(sc.pw, fft_root(exp, inverse));
+  sc.one = fr_one();
+  fr_store(sc.minv, fr_inv(fr_from_u64((uint64_t)1 << exp)));
+}
 hipError_t launch_group_fft(bool g2, const void* d_in, uint32_t exp, void* d_out, bool inverse, bool pairing,
                             const FftScalars& sc, void* d_work, unsigned long long* d_key, hipStream_t stream);
 // h[i] = tau_g1[m + i] - tau_g1[i], i < m - 1: ark G1 records in, pairing BE records out
@@ -101,5 +113,29 @@ hipError_t launch_poly_divide(const void* d_coeffs, uint64_t n, const fr_powers<
 // KZG10::open's last step: the two evaluations (64 B at d_values) behind the proof's point, unless
 // the MSM's load rejected a base
 hipError_t launch_open_emit(const void* d_values, void* d_out64, const unsigned long long* d_key, hipStream_t stream);
+
+// Fr NTT (ntt_kernels.hip). The scalars of one transform, computed on the host (domain.hip) with
+// csrc/fr.hpp. d_tw: the plan's twiddle tables (tw_bytes); d_stage: the plan's staging array
+// (stage_bytes), needed only where d_out is d_in and the plan has more than one pass. d_key
+// (optional): the bad key of the call the transform is part of; once it reports a rejection the
+// passes write nothing.
+struct NttScalars {
+  fr pw[26];  // w^(+-2^k) in Montgomery form
+  fr one;     // Montgomery 1
+  fr scale;   // the plain integer every output is multiplied by: 1, 1/m, or another canonical factor
+};
+hipError_t launch_fr_ntt(const NttPlan& p, const void* d_in, void* d_out, const NttScalars& sc, void* d_tw, void* d_stage,
+                         const unsigned long long* d_key, hipStream_t stream);
+
+// amortized openings, the group side (fft_kernels.hip). The table: powers reversed and padded with
+// n points at infinity, forward transform of 2n points (sc: its scalars); d_work:
+// open_domain_table_workspace_bytes. The proofs: steps Load .. Emit of open_domain_plan over the 2n
+// scalars the NTT left at the plan's `scalars` (wide: the scalars of the inverse transform of 2n
+// points, out: of the forward transform of n points).
+hipError_t launch_open_domain_table(bool g2, const void* d_powers, uint32_t exp, void* d_table, const FftScalars& sc,
+                                    void* d_work, unsigned long long* d_key, hipStream_t stream);
+hipError_t launch_open_domain_step(bool g2, const OpenDomainPlan& p, DomainStep step, const void* d_table, void* d_proofs,
+                                   const FftScalars& wide, const FftScalars& out, void* d_work, unsigned long long* d_key,
+                                   hipStream_t stream);
 
 }  // namespace kzgpot

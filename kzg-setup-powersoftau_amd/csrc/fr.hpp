@@ -2,8 +2,9 @@
 // little-endian words, Montgomery form with R = 2^256, one CIOS multiply. The ABI units start from
 // the host helpers at the end (phase2.hip: the domain root, the powers w^(+-2^k), 1/m; open.hip: the
 // powers z^(2^k)); the kernels use the arithmetic (fft_kernels.hip: k_fft_twiddles builds w^j from
-// those powers; poly_kernels.hip: the polynomial division of KZG10 open). Nothing here is hot: ~31
-// multiplies per twiddle against the 254 point doublings the twiddle then drives.
+// those powers; poly_kernels.hip: the polynomial division of KZG10 open; ntt_kernels.hip: the NTT's
+// butterflies, the one place where these multiplies are the hot path). Elsewhere nothing here is
+// hot: ~31 multiplies per twiddle against the 254 point doublings the twiddle then drives.
 //
 // Plain C++17 unless the compiler is hipcc, so a host program can include this file alone
 // (tests/host_units/fr_units.cpp, built by g++ with and without sanitizers).
@@ -81,6 +82,23 @@ KZG_HD constexpr void fr_add(fr& out, const fr& a, const fr& b) {
   }
   t[8] = (uint32_t)c;
   fr_cond_sub(out, t);
+}
+
+// out = a - b mod r for a, b < r
+KZG_HD constexpr void fr_sub(fr& out, const fr& a, const fr& b) {
+  uint32_t d[8] = {};
+  uint32_t br = 0;
+  for (int i = 0; i < 8; i++) {
+    const uint64_t s = (uint64_t)a.v[i] - b.v[i] - br;  // wraps mod 2^64 on a borrow: bit 32 is then set
+    d[i] = (uint32_t)s;
+    br = (uint32_t)(s >> 32) & 1u;
+  }
+  uint32_t c = 0;  // a < b: the difference wrapped mod 2^256, and adding r wraps it back
+  for (int i = 0; i < 8; i++) {
+    const uint64_t s = (uint64_t)d[i] + (br ? FR_R[i] : 0u) + c;
+    out.v[i] = (uint32_t)s;
+    c = (uint32_t)(s >> 32);
+  }
 }
 
 // R = 2^256 mod r (the Montgomery one) and R^2 mod r, by 256 and 512 doublings at compile time

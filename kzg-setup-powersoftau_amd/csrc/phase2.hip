@@ -9,17 +9,6 @@ using namespace kzgpot;
 
 namespace {
 
-// The scalars of one transform of size m = 2^exp: the powers w^(+-2^k) (the inverse uses
-// w^-1 = w^(m-1)) and 1/m
-void fft_scalars(uint32_t exp, bool inverse, FftScalars& sc) {
-  const uint64_t m = (uint64_t)1 << exp;
-  fr w = fr_domain_root(exp);
-  if (inverse) w = fr_pow(w, fr{{(uint32_t)(m - 1), 0, 0, 0, 0, 0, 0, 0}});  // m - 1 < 2^32
-  fr_fill_powers(sc.pw, w);
-  sc.one = fr_one();
-  fr_store(sc.minv, fr_inv(fr_from_u64(m)));
-}
-
 constexpr uint32_t kFftFlags = KZGPOT_FFT_INVERSE | KZGPOT_FFT_OUT_PAIRING;
 
 // host_key (optional): receives the bad key once the transform is done

@@ -1,12 +1,14 @@
 // The launch plans of the group FFT (fft_kernels.hip), the multi-scalar multiplication
-// (msm_kernels.hip), the polynomial division (poly_kernels.hip) and KZG10 open (open.hip), each stated
-// once: where every kernel reads and writes inside the caller-supplied workspace, and the launch
-// schedule as data (one entry per stage, level or step, in launch order). The launchers run the
-// tables; nothing else decides an offset or a lane count.
+// (msm_kernels.hip), the polynomial division (poly_kernels.hip), KZG10 open (open.hip), the Fr NTT
+// (ntt_kernels.hip) and the amortized openings over a domain (domain.hip), each stated once: where
+// every kernel reads and writes inside the caller-supplied workspace, and the launch schedule as
+// data (one entry per stage, level or step, in launch order). The launchers run the tables; nothing
+// else decides an offset or a lane count.
 //
 // Plain C++17 with no HIP header, so a host program can include this file alone
 // (tests/host_units/plan_units.cpp, built by g++ with and without sanitizers; tests/test_plan_units.py
-// checks every launch's reads and writes against its regions).
+// checks every launch's reads and writes against its regions; tests/host_units/ntt_units.cpp and
+// tests/test_ntt_units.py do the same for the last two plans).
 #pragma once
 #include <stdint.h>
 
@@ -287,6 +289,127 @@ inline OpenPlan open_plan(uint64_t n, uint64_t n_blind, uint32_t flags) {
   p.bytes = o;
   p.ok = true;
   return p;
+}
+
+// ---------------------------------------------------------------- Fr NTT
+// A transform of m = 2^exp elements in passes (ntt_kernels.hip): a block of 256 lanes holds
+// 2^tl = 2^min(t, exp) elements in LDS and runs the stages [q0, q0 + c) of the decimation-in-time
+// schedule on them (stage q: half-block 2^q over the bit-reversed input), greedily c = min(t, what
+// is left). A block's slot s = (k << lb) | l has k < 2^c along the pass's stages at element
+// stride 2^q0 and l < 2^lb (lb = tl - c) consecutive elements; the other index bits are the
+// block's (ntt_parts.hpp states the arithmetic). Pass 0 has lb = 0 and reads the caller's input
+// bit-reversed; the other passes read and write the same elements.
+//
+// Workspace: two twiddle tables, lo[j] = w^j for j < 2^lo_bits and hi[j] = w^(j << lo_bits) for
+// j < 2^hi_bits, lo_bits + hi_bits = exp - 1 split evenly (w^e = lo hi, one extra multiply; 384 KB
+// at exp 26), and the staging array of m elements that pass 0 writes when the caller's output is
+// its input and there is more than one pass (otherwise pass 0 writes the output itself).
+// kNttTile: the tile that measured fastest at 2^22 (profiles/open_domain_timing.json)
+constexpr uint32_t kNttMaxExp = 26, kNttTileMin = 8, kNttTileMax = 11, kNttTile = 9;
+constexpr uint32_t kNttMaxPasses = 4;  // ceil(26 / 8)
+constexpr uint32_t kNttFlags = KZGPOT_NTT_INVERSE | KZGPOT_POLY_TILE(0xf);
+static_assert(kNttMaxPasses * kNttTileMin >= kNttMaxExp, "pass[] holds every pass of the largest transform");
+static_assert((32u << kNttTileMax) <= 65536, "the largest tile is the 64 KB of LDS the kernel declares");
+// the NTT's flags -> its tile (the library's for 0); false: an unknown bit or an unsupported tile
+inline bool ntt_flags(uint32_t flags, uint32_t& t) {
+  t = (flags >> 16) & 0xfu;
+  if (!t) t = kNttTile;
+  return t >= kNttTileMin && t <= kNttTileMax && !(flags & ~kNttFlags);
+}
+struct NttPass {
+  uint32_t q0, c, lb;  // first stage, stages, log2 of the run of consecutive elements
+  uint64_t stride;     // 2^q0: the element stride along the pass's stages
+  uint64_t blocks;     // m >> tl
+};
+struct NttPlan {
+  uint32_t exp, t, tl, npass;
+  NttPass pass[kNttMaxPasses];
+  uint32_t lo_bits, hi_bits;
+  uint64_t tw_lo, tw_hi, tw_bytes;  // byte offsets of the tables; what both take (the staging array's offset)
+  uint64_t stage_bytes, bytes;      // bytes = tw_bytes + stage_bytes; 0: invalid arguments
+};
+inline NttPlan ntt_plan(uint32_t exp, uint32_t t) {
+  NttPlan p = {};
+  if (exp > kNttMaxExp || t < kNttTileMin || t > kNttTileMax) return p;
+  p.exp = exp, p.t = t, p.tl = exp < t ? exp : t;
+  for (uint32_t q0 = 0; q0 < exp || !p.npass;) {
+    const uint32_t c = exp - q0 < t ? exp - q0 : t;
+    p.pass[p.npass++] = NttPass{q0, c, p.tl - c, (uint64_t)1 << q0, ((uint64_t)1 << exp) >> p.tl};
+    q0 += c;
+    if (!c) break;  // exp = 0: one pass without a stage
+  }
+  const uint32_t e = exp ? exp - 1 : 0;  // twiddle exponents are below m / 2
+  p.lo_bits = (e + 1) / 2, p.hi_bits = e / 2;
+  p.tw_lo = 0;
+  p.tw_hi = align256((uint64_t)32 << p.lo_bits);
+  p.tw_bytes = p.tw_hi + align256((uint64_t)32 << p.hi_bits);
+  p.stage_bytes = p.npass > 1 ? (uint64_t)32 << exp : 0;
+  p.bytes = p.tw_bytes + p.stage_bytes;
+  return p;
+}
+inline uint64_t ntt_workspace_bytes(uint32_t exp, uint32_t t) { return ntt_plan(exp, t).bytes; }
+
+// ---------------------------------------------------------------- amortized KZG10 opening (FK20)
+// All n = 2^exp proofs of one polynomial from the table T of 2n points. Workspace:
+// the NTT's input (2n elements: the shifted coefficients, later the coefficients themselves), its
+// output (the 2n scalars of the per-point pass), its twiddle tables (sized for the size-2n transform; the
+// size-n transform builds its own there afterwards; no staging array: neither runs in place), the work
+// rows of the 2n-point and the n-point group transform, and their twiddle tables.
+constexpr uint32_t kOpenDomainMaxExp = 24;
+enum class DomainStep : uint32_t {
+  ScalarsNtt,  // b -> v / 2n
+  Load,        // k_fft_load of T into rows_a
+  PointMul,    // rows_a[t] *= scalars[bitrev(t)]
+  StagesWide,  // the 2n-point inverse stages, no scale pass
+  Gather,      // rows_a[n - 1 + k] -> rows_b[bitrev_n(k)]
+  StagesOut,   // the n-point forward stages
+  Emit,        // rows_b -> proofs
+  ValuesNtt,   // c -> values (skipped where the caller wants none)
+};
+constexpr uint32_t kDomainSteps = 8;
+struct OpenDomainPlan {
+  uint32_t exp, t;
+  uint64_t n, rec;
+  uint64_t ntt_in, scalars, ntt_tw, rows_a, rows_b, tw_a, tw_b, bytes;  // byte offsets
+  uint64_t gather_src, gather_dst, gather_cnt;  // rows [src, src + cnt) of rows_a -> rows [dst, dst + cnt) of rows_b
+  DomainStep step[kDomainSteps];
+  bool ok;
+};
+inline OpenDomainPlan open_domain_plan(bool g2, uint32_t exp, uint32_t t) {
+  OpenDomainPlan p = {};
+  const NttPlan ntt = ntt_plan(exp + 1, t);
+  if (exp > kOpenDomainMaxExp || !ntt.bytes) return p;
+  p.exp = exp, p.t = t;
+  p.n = (uint64_t)1 << exp;
+  p.rec = point_record(g2);
+  uint64_t o = 0;
+  p.ntt_in = o, o += align256(2 * p.n * 32);
+  p.scalars = o, o += align256(2 * p.n * 32);
+  p.ntt_tw = o, o += ntt.tw_bytes;
+  p.rows_a = o, o += align256(2 * p.n * work_rows(g2) * 4);
+  p.rows_b = o, o += align256(p.n * work_rows(g2) * 4);
+  p.tw_a = o, o += fft_twiddle_bytes(exp + 1);
+  p.tw_b = o, o += fft_twiddle_bytes(exp);
+  p.bytes = o;
+  p.gather_src = p.n - 1, p.gather_dst = 0, p.gather_cnt = p.n;
+  const DomainStep steps[kDomainSteps] = {DomainStep::ScalarsNtt, DomainStep::Load,      DomainStep::PointMul,
+                                          DomainStep::StagesWide, DomainStep::Gather,    DomainStep::StagesOut,
+                                          DomainStep::Emit,       DomainStep::ValuesNtt};
+  for (uint32_t k = 0; k < kDomainSteps; k++) p.step[k] = steps[k];
+  p.ok = true;
+  return p;
+}
+// the opening's flags: KZGPOT_POLY_TILE alone, handed to the NTT
+inline bool open_domain_flags(uint32_t flags, uint32_t& t) {
+  return ntt_flags(flags, t) && !(flags & KZGPOT_NTT_INVERSE);
+}
+inline uint64_t open_domain_workspace_bytes(bool g2, uint32_t exp, uint32_t flags) {
+  uint32_t t;
+  return open_domain_flags(flags, t) ? open_domain_plan(g2, exp, t).bytes : 0;
+}
+// the table: the work rows and twiddles of one forward transform of 2n points
+inline uint64_t open_domain_table_workspace_bytes(bool g2, uint32_t exp) {
+  return exp > kOpenDomainMaxExp ? 0 : fft_workspace_bytes(g2, exp + 1);
 }
 
 }  // namespace kzgpot

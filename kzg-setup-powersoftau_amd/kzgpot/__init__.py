@@ -649,3 +649,125 @@ def kzg_open(powers, coeffs, z, blinding=None, window: int = 0, tile: int = 0) -
                                mont=True, window=window, tile=tile))
     return KzgProof(out[:96], int.from_bytes(out[128:], "little") if blinding is not None else None,
                     int.from_bytes(out[96:128], "little"))
+
+
+# ------------------------------------------------------------------ Fr NTT, amortized openings over a domain (FK20)
+NTT_INVERSE = 0x1
+NTT_MAX_EXP, NTT_TILES, OPEN_DOMAIN_MAX_EXP = 26, range(8, 12), 24
+NTT_DEFAULT_TILE = 9  # kNttTile (csrc/plans.hpp); tests/test_gpu_ntt.py holds the two together
+
+
+def ntt_flags(inverse: bool = False, tile: int = 0) -> int:
+    """KZGPOT_NTT_INVERSE | KZGPOT_POLY_TILE(tile): 2^tile elements per block, 8 <= tile <= 11; 0: the library's."""
+    if tile and tile not in NTT_TILES:
+        raise ValueError(f"ntt: tile {tile}")
+    return (NTT_INVERSE if inverse else 0) | (tile << 16)
+
+
+def fr_ntt_workspace(exp: int, flags: int = 0) -> int:
+    return int(_lib.load().kzgpot_fr_ntt_workspace(exp, flags))
+
+
+def fr_ntt(values, exp: int, inverse: bool = False, tile: int = 0) -> bytes:
+    """The NTT over Fr of 2^exp values (32-byte little-endian integers as bytes, or Python ints in
+    [0, 2^256), each reduced mod r) on the domain generated by fr_domain_root(exp), natural order
+    in and out: out[i] = sum_j values[j] w^(ij), or with inverse=True 1/m sum_j values[j] w^(-ij).
+    Returns the 2^exp canonical 32-byte little-endian values."""
+    data = _scalar_bytes(values)
+    if not 0 <= exp <= NTT_MAX_EXP or len(data) != 32 << exp:
+        raise ValueError(f"fr_ntt: {len(data)} B for 2^{exp} values")
+    out = ctypes.create_string_buffer(len(data))
+    r = _lib.load().kzgpot_fr_ntt(data, exp, out, ntt_flags(inverse, tile))
+    if r:
+        raise KzgPotError(r)
+    return out.raw
+
+
+def open_domain_table_workspace(g2: bool, exp: int) -> int:
+    return int(_lib.load().kzgpot_open_domain_table_workspace(int(g2), exp))
+
+
+def open_domain_workspace(g2: bool, exp: int, flags: int = 0) -> int:
+    return int(_lib.load().kzgpot_open_domain_workspace(int(g2), exp, flags))
+
+
+def _domain_exp(exp: int, what: str) -> None:
+    if not 0 <= exp <= OPEN_DOMAIN_MAX_EXP:
+        raise ValueError(f"{what}: exp {exp} outside 0..{OPEN_DOMAIN_MAX_EXP}")
+
+
+def _open_domain_table(g2: bool, records, exp: int) -> CodecResult:
+    _domain_exp(exp, "open domain table")
+    rec = 192 if g2 else 96
+    ptr, nbytes, keep = _buf(records)
+    if nbytes < rec << exp:
+        raise ValueError(f"open domain table: {nbytes} B is less than 2^{exp} records of {rec} B")
+    out = ctypes.create_string_buffer(2 * rec << exp)
+    fb = ctypes.c_int64(-1)
+    fn = _lib.load().kzgpot_g2_open_domain_table if g2 else _lib.load().kzgpot_g1_open_domain_table
+    ret = fn(ptr, exp, out, ctypes.byref(fb))
+    del keep
+    if ret <= -100:
+        raise KzgPotError(ret)
+    return CodecResult(out.raw if ret == 0 else b"", ret, fb.value, None)
+
+
+def open_domain_table(records, exp: int, g2: bool = False) -> bytes:
+    """The table of the amortized opening over the domain of size n = 2^exp: 2n ark-uncompressed
+    records that depend on the setup and exp only. `records`: at least n packed ark-uncompressed
+    records [tau^j]G, powers_of_g (G1) or, with g2=True, powers_of_h. A malformed record raises
+    KzgPotError with its index."""
+    return _checked(_open_domain_table(g2, records, exp))
+
+
+def _open_domain(g2: bool, table, coeffs, exp: int, tile: int, want_values: bool) -> CodecResult:
+    _domain_exp(exp, "open domain")
+    rec = 192 if g2 else 96
+    ptr, nbytes, keep = _buf(table)
+    sc = _scalar_bytes(coeffs)
+    n = 1 << exp
+    if nbytes != 2 * n * rec or len(sc) % 32 or len(sc) > 32 * n:
+        raise ValueError(f"open domain: a table of {nbytes} B and {len(sc)} B of coefficients for 2^{exp} points")
+    proofs = ctypes.create_string_buffer(n * rec)
+    values = ctypes.create_string_buffer(n * 32) if want_values else None
+    fb = ctypes.c_int64(-1)
+    fn = _lib.load().kzgpot_g2_open_domain if g2 else _lib.load().kzgpot_g1_open_domain
+    ret = fn(ptr, sc, len(sc) // 32, exp, proofs, values, ntt_flags(False, tile), ctypes.byref(fb))
+    del keep
+    if ret <= -100:
+        raise KzgPotError(ret)
+    return CodecResult((proofs.raw + (values.raw if want_values else b"")) if ret == 0 else b"", ret, fb.value, None)
+
+
+def g1_open_domain(table, coeffs, exp: int, tile: int = 0, want_values: bool = True) -> CodecResult:
+    """kzgpot_g1_open_domain on a packed table and coefficients as given (no trimming): `out` is the
+    2^exp proofs (96 B each) followed, unless want_values=False, by the 2^exp values (32 B each); a
+    malformed table record gives ret = -(status), first_bad = its index and out = b""."""
+    return _open_domain(False, table, coeffs, exp, tile, want_values)
+
+
+def g2_open_domain(table, coeffs, exp: int, tile: int = 0, want_values: bool = True) -> CodecResult:
+    return _open_domain(True, table, coeffs, exp, tile, want_values)
+
+
+@dataclass
+class DomainProofs:
+    """The openings of one polynomial at every point w^i of the domain of size 2^exp: `proofs` the
+    2^exp packed ark-uncompressed records [(p(tau) - p(w^i)) / (tau - w^i)]G in natural order,
+    `values` the p(w^i) (None: not asked for)."""
+    proofs: bytes
+    values: list[int] | None
+
+
+def kzg_open_domain(table, coeffs, exp: int, g2: bool = False, tile: int = 0, want_values: bool = True) -> DomainProofs:
+    """All 2^exp non-hiding KZG10 opening proofs of p at once (Feist-Khovratovich) from
+    open_domain_table's table: what kzg_open gives as `w` for z = w^i, i < 2^exp, at the cost of two
+    group FFTs. `coeffs` are ints mod r, lowest degree first, at most 2^exp after the trailing
+    zeros are dropped (as kzg_commit and kzg_open drop them)."""
+    p = _trimmed(coeffs)
+    if len(p) > 1 << max(0, min(exp, OPEN_DOMAIN_MAX_EXP)):
+        raise ValueError(f"kzg_open_domain: degree {len(p) - 1} does not fit the domain of size 2^{exp}")
+    out = _checked(_open_domain(g2, table, p, exp, tile, want_values))
+    cut = (192 if g2 else 96) << exp
+    values = [int.from_bytes(out[o: o + 32], "little") for o in range(cut, len(out), 32)] if want_values else None
+    return DomainProofs(out[:cut], values)

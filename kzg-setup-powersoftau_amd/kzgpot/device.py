@@ -238,3 +238,84 @@ def g1_kzg_open_dev(d_powers_of_g: torch.Tensor, d_coeffs: torch.Tensor, z: int,
     if rc:
         raise RuntimeError(f"kzg open: launch failed ({rc})")
     return work
+
+
+def fr_ntt_dev(d_in: torch.Tensor, exp: int, d_out: torch.Tensor, inverse: bool = False, tile: int = 0,
+               work: torch.Tensor | None = None) -> torch.Tensor:
+    """Asynchronous NTT over Fr on device tensors (torch's current stream): 2^exp 32-byte
+    little-endian values in, as many canonical values out; d_out may be d_in. Allocates the
+    workspace (kzgpot_fr_ntt_workspace bytes) unless `work` is given; returns it — keep it alive
+    until the stream has run the call."""
+    if d_in.numel() != 32 << exp or d_out.numel() < 32 << exp:
+        raise ValueError(f"ntt: bad buffer sizes {d_in.numel()} / {d_out.numel()}")
+    if not (d_in.is_cuda and d_out.is_cuda):
+        raise ValueError("fr_ntt_dev needs device tensors")
+    lib = _lib.load()
+    flags = (1 if inverse else 0) | (tile << 16)
+    need = int(lib.kzgpot_fr_ntt_workspace(exp, flags))
+    if need == 0:
+        raise ValueError(f"ntt: exp = {exp} with tile {tile} is not supported")
+    work = _work(need, work, d_out.device, "ntt")
+    rc = lib.kzgpot_fr_ntt_dev(d_in.data_ptr(), exp, d_out.data_ptr(), flags, work.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"ntt: launch failed ({rc})")
+    return work
+
+
+def open_domain_table_dev(g2: bool, d_powers: torch.Tensor, exp: int, d_table: torch.Tensor, key: torch.Tensor,
+                          work: torch.Tensor | None = None) -> torch.Tensor:
+    """Asynchronous table of the amortized opening (torch's current stream): the first 2^exp ark
+    records of d_powers in, 2^(exp+1) records into d_table. Workspace as the other calls'."""
+    rec = 192 if g2 else 96
+    if d_powers.numel() < rec << exp or d_table.numel() < 2 * rec << exp:
+        raise ValueError(f"open domain table: bad buffer sizes {d_powers.numel()} / {d_table.numel()}")
+    if not (d_powers.is_cuda and d_table.is_cuda and key.is_cuda):
+        raise ValueError("open_domain_table_dev needs device tensors")
+    lib = _lib.load()
+    need = int(lib.kzgpot_open_domain_table_workspace(int(g2), exp))
+    if need == 0:
+        raise ValueError(f"open domain table: exp = {exp} is not supported")
+    work = _work(need, work, d_table.device, "open domain table")
+    fn = lib.kzgpot_g2_open_domain_table_dev if g2 else lib.kzgpot_g1_open_domain_table_dev
+    rc = fn(d_powers.data_ptr(), exp, d_table.data_ptr(), work.data_ptr(), key.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"open domain table: launch failed ({rc})")
+    return work
+
+
+def open_domain_dev(g2: bool, d_table: torch.Tensor, d_coeffs: torch.Tensor, exp: int, d_proofs: torch.Tensor,
+                    d_values: torch.Tensor | None, key: torch.Tensor, tile: int = 0,
+                    work: torch.Tensor | None = None) -> torch.Tensor:
+    """Asynchronous amortized opening on device tensors (torch's current stream): the table of
+    2^(exp+1) records and at most 2^exp 32-byte coefficients in, 2^exp proof records into d_proofs
+    and (unless None) 2^exp 32-byte values into d_values. Allocates the workspace
+    (kzgpot_open_domain_workspace bytes) unless `work` is given; returns it — keep it alive until
+    the stream has run the call."""
+    rec = 192 if g2 else 96
+    n, nc = 1 << exp, d_coeffs.numel() // 32
+    if (d_table.numel() != 2 * n * rec or d_coeffs.numel() != 32 * nc or d_proofs.numel() < n * rec
+            or (d_values is not None and d_values.numel() < 32 * n)):
+        raise ValueError(f"open domain: bad buffer sizes {d_table.numel()} / {d_coeffs.numel()} / {d_proofs.numel()}")
+    tensors = [d_table, d_coeffs, d_proofs, key] + ([d_values] if d_values is not None else [])
+    if not all(t.is_cuda for t in tensors):
+        raise ValueError("open_domain_dev needs device tensors")
+    lib = _lib.load()
+    flags = tile << 16
+    need = int(lib.kzgpot_open_domain_workspace(int(g2), exp, flags))
+    if need == 0 or nc > n:
+        raise ValueError(f"open domain: exp = {exp}, {nc} coefficients with tile {tile} is not supported")
+    work = _work(need, work, d_proofs.device, "open domain")
+    fn = lib.kzgpot_g2_open_domain_dev if g2 else lib.kzgpot_g1_open_domain_dev
+    rc = fn(d_table.data_ptr(), d_coeffs.data_ptr() if nc else None, nc, exp, d_proofs.data_ptr(),
+            d_values.data_ptr() if d_values is not None else None, flags, work.data_ptr(), key.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"open domain: launch failed ({rc})")
+    return work
+
+
+def g1_open_domain_dev(d_table, d_coeffs, exp, d_proofs, d_values, key, **kw) -> torch.Tensor:
+    return open_domain_dev(False, d_table, d_coeffs, exp, d_proofs, d_values, key, **kw)
+
+
+def g2_open_domain_dev(d_table, d_coeffs, exp, d_proofs, d_values, key, **kw) -> torch.Tensor:
+    return open_domain_dev(True, d_table, d_coeffs, exp, d_proofs, d_values, key, **kw)

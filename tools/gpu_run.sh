@@ -36,6 +36,10 @@
 #                 all-equal-scalar row at 2^20; one process)
 #   open          tools/open_timing.py (the polynomial division at 2^20 / 2^24 against a copy of its bytes,
 #                 KZG10 open at 2^20 and the MSM alone over the same bases; one process)
+#   open_domain   tools/open_domain_timing.py (the Fr NTT at 2^16 .. 2^24 with every tile against a copy, the
+#                 amortized opening at G1 2^16 / 2^20 and G2 2^16 against its two group transforms; one process)
+#   open_domain_trace  the G1 part of that under rocprofv3 --kernel-trace, summed per kernel and grid by
+#                 tools/trace_summary.py (the per-point pass beside the scale pass it replaces)
 set -o pipefail
 tag=${1:?usage: gpu_run.sh TAG STEP [STEP ...]}
 shift
@@ -86,6 +90,13 @@ for step in "$@"; do
     lagrange) timeout -k 10 500 python3 -u tools/lagrange_timing.py > ${o}_lagrange.json 2> ${o}_lagrange.err ;;
     msm) timeout -k 10 500 python3 -u tools/msm_timing.py > ${o}_msm_timing.json 2> ${o}_msm_timing.err ;;
     open) timeout -k 10 500 python3 -u tools/open_timing.py > ${o}_open_timing.json 2> ${o}_open_timing.err ;;
+    open_domain) timeout -k 10 500 python3 -u tools/open_domain_timing.py > ${o}_open_domain_timing.json \
+                   2> ${o}_open_domain_timing.err ;;
+    open_domain_trace) timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d ${o}_open_domain_trace -o run \
+                         -- python3 tools/open_domain_timing.py --ntt "" --g1 16,20 --g2 "" \
+                         > ${o}_open_domain_traced.json 2> ${o}_open_domain_traced.err &&
+                       python3 tools/trace_summary.py "$(find ${o}_open_domain_trace -name '*kernel_trace.csv' | head -1)" \
+                         --out ${o}_open_domain_kernel_trace.csv > /dev/null ;;
     *) echo "[gpu_run] unknown step $step" >&2; exit 2 ;;
   esac
   rc=$?
