@@ -414,6 +414,73 @@ int kzgpot_g1_open_domain(const uint8_t* table, const uint8_t* coeffs, uint64_t 
 int kzgpot_g2_open_domain(const uint8_t* table, const uint8_t* coeffs, uint64_t n_coeffs, uint32_t exp,
                           uint8_t* proofs, uint8_t* values, uint32_t flags, int64_t* first_bad);
 
+/* ---------------------------------------------------------------- evaluation form: batch inversion, KZG10 open */
+/* Scalars here are 32 little-endian bytes; an input is any 256-bit integer and is reduced mod r
+ * (2^256 - 1 is legal and means its residue), an output is canonical (below r). Vectors over the
+ * domain of size n = 2^exp generated by w = kzgpot_fr_domain_root(exp) are in natural order: entry i
+ * belongs to w^i, the order of kzgpot_fr_ntt, of kzgpot_g1_fft's output and of
+ * kzgpot_g1_open_domain's values.
+ *   KZGPOT_POLY_TILE(t): entries per 256-lane block, 2^t with 8 <= t <= 12, as for the division; 0:
+ *     the library's tile (2^11). No result depends on it.
+ *
+ * Batch inversion: out[i] = in[i]^-1 mod r, and out[i] = 0 where in[i] = 0 mod r (the convention of
+ * ark-ff's batch_inversion). n <= 2^26 entries; out may be in. One field inversion per tile.
+ * n > 2^26, an unknown flag bit, a tile outside 8..12 or a NULL pointer where n is non-zero is
+ * KZGPOT_E_INVALID_ARG before any device use. */
+/* Asynchronous on `stream`: d_in and d_out (16-byte aligned) in HBM; no workspace. */
+int kzgpot_fr_batch_inverse_dev(const void* d_in, uint64_t n, void* d_out, uint32_t flags, void* stream);
+/* The same on host buffers, synchronous, on the current device. */
+int kzgpot_fr_batch_inverse(const uint8_t* in, uint64_t n, uint8_t* out, uint32_t flags);
+
+/* Division by (x - z) in evaluation form. evals[i] = p(w^i), i < n = 2^exp, for a polynomial p of
+ * degree below n; z any 256-bit integer.
+ *   value      p(z)
+ *   quotient   the n evaluations q_i of (p(x) - p(z)) / (x - z) on the same domain. May be NULL:
+ *              evaluate only. It must not overlap evals.
+ * z off the domain (z^n != 1):  value = (z^n - 1)/n sum_i e_i w^i / (z - w^i),  q_i = (value - e_i) / (z - w^i).
+ * z = w^m:  value = e_m,  q_i = (value - e_i) / (z - w^i) for i != m,  q_m = - sum_{i != m} q_i w^(i-m).
+ * n = 1: the domain is {1}; the value is e_0 and the quotient [0] for every z.
+ * The n differences z - w^i are inverted by the batch inversion's tile routine. exp > 26, an unknown
+ * flag bit, a tile outside 8..12 or a NULL pointer is KZGPOT_E_INVALID_ARG before any device use. */
+/* Host only. Bytes of device memory (d_work) the division needs: 32 n for the inverted differences,
+ * two partial sums per tile, 256 more; monotone in exp; 0 for invalid arguments. */
+uint64_t kzgpot_fr_evals_workspace(uint32_t exp, uint32_t flags);
+/* Asynchronous on `stream`: d_evals, d_quotient, d_value (16-byte aligned) and d_work in HBM; z_le32
+ * is read on the host before the call returns. */
+int kzgpot_fr_evals_divide_dev(const void* d_evals, uint32_t exp, const uint8_t z_le32[32], void* d_quotient,
+                               void* d_value, uint32_t flags, void* d_work, void* stream);
+/* The same on host buffers, synchronous, on the current device. */
+int kzgpot_fr_evals_divide(const uint8_t* evals, uint32_t exp, const uint8_t z_le32[32], uint8_t* quotient,
+                           uint8_t value_le32[32], uint32_t flags);
+
+/* KZG10 open from evaluations: the proof that p(z) = value for the commitment
+ * sum_i [e_i] lagrange[i] (kzgpot_g1_msm over the same basis), without the coefficients of p.
+ * lagrange: the n = 2^exp records [L_i(tau)]G of the Lagrange basis, natural order: kzgpot_g1_fft
+ * (inverse) of the first n records of powers_of_g. out, 128 bytes:
+ *   [0, 96)    w = sum_i [q_i] lagrange[i], an ark-uncompressed G1 record; q the quotient above. For
+ *              every z, on the domain or off it, it is the w of kzgpot_g1_kzg_open for the coefficients of p.
+ *   [96, 128)  value = p(z), little-endian, canonical
+ * The quotient stays in the workspace and w is ONE multi-scalar multiplication over the caller's
+ * records where they lie (no staging copy: there is one base range).
+ *   flags: KZGPOT_MSM_BASES_MONT and KZGPOT_MSM_WINDOW(c) as for the MSM, KZGPOT_POLY_TILE(t) as above.
+ *   bases: all n records are read and checked as the MSM checks them: -(status) with the smallest
+ *     index of a malformed record, and a rejected call writes nothing.
+ * KZGPOT_E_INVALID_ARG, before any device use: a NULL pointer, an unknown flag bit, a tile outside
+ * 8..12, exp > 26, or n bases above what the MSM takes at that width; the workspace function then
+ * returns 0.
+ * Hiding proofs are out of scope: the blinding quotient lives over powers_of_gamma_g, which the
+ * loaders hold as 104-byte Montgomery rows while the Lagrange basis is 96-byte ark records, and one
+ * MSM takes one record format. */
+/* Host only. Bytes of d_work for these arguments; 0 when they are invalid. */
+uint64_t kzgpot_kzg_open_evals_workspace(uint32_t exp, uint32_t flags);
+/* Asynchronous on `stream`: every d_ pointer in HBM, d_evals, d_out (128 B) and d_work 16-byte
+ * aligned. d_bad_key as for kzgpot_g1_msm_dev. */
+int kzgpot_g1_kzg_open_evals_dev(const void* d_lagrange, const void* d_evals, uint32_t exp, const uint8_t z_le32[32],
+                                 void* d_out, uint32_t flags, void* d_work, uint64_t* d_bad_key, void* stream);
+/* The same on host buffers, synchronous, on the current device. */
+int kzgpot_g1_kzg_open_evals(const uint8_t* lagrange, const uint8_t* evals, uint32_t exp, const uint8_t z_le32[32],
+                             uint8_t out[128], uint32_t flags, int64_t* first_bad);
+
 /* ---------------------------------------------------------------- BN254 (config 5, next-row §8f 4) */
 /* No reference counterpart: the same path instantiated for ark-bn254 0.2 G1 (cofactor 1).
  * ark compressed (32 B: x LE, SWFlags bit7 PositiveY / bit6 Infinity in byte 31) → ark

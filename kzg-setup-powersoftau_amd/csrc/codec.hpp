@@ -114,6 +114,17 @@ hipError_t launch_poly_divide(const void* d_coeffs, uint64_t n, const fr_powers<
 // the MSM's load rejected a base
 hipError_t launch_open_emit(const void* d_values, void* d_out64, const unsigned long long* d_key, hipStream_t stream);
 
+// evaluation form (eval_kernels.hip). out[i] = in[i]^-1 mod r, 0 for a zero; n <= kEvalMaxN entries
+// of 32 B (any 256-bit integers in, canonical values out), out may be in; t as for the division.
+hipError_t launch_fr_batch_inverse(const void* d_in, uint64_t n, void* d_out, uint32_t t, hipStream_t stream);
+// Division by (x - z) from the 2^exp evaluations of eval_plan p: value = p(z) (32 B, canonical) and,
+// unless d_quotient is null, the quotient's 2^exp evaluations (canonical; not over d_evals). sc:
+// fr_eval_setup's scalars for (p.exp, z), computed on the host (evals.hip). d_work: p.bytes.
+hipError_t launch_evals_divide(const EvalPlan& p, const void* d_evals, const fr_eval_scalars& sc, void* d_quotient,
+                               void* d_value, void* d_work, hipStream_t stream);
+// the open's last step: the value (32 B) behind the proof's point, unless the MSM's load rejected a base
+hipError_t launch_evals_emit(const void* d_value, void* d_out32, const unsigned long long* d_key, hipStream_t stream);
+
 // Fr NTT (ntt_kernels.hip). The scalars of one transform, computed on the host (domain.hip) with
 // csrc/fr.hpp. d_tw: the plan's twiddle tables (tw_bytes); d_stage: the plan's staging array
 // (stage_bytes), needed only where d_out is d_in and the plan has more than one pass. d_key

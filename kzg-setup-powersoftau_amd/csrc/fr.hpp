@@ -3,11 +3,13 @@
 // the host helpers at the end (phase2.hip: the domain root, the powers w^(+-2^k), 1/m; open.hip: the
 // powers z^(2^k)); the kernels use the arithmetic (fft_kernels.hip: k_fft_twiddles builds w^j from
 // those powers; poly_kernels.hip: the polynomial division of KZG10 open; ntt_kernels.hip: the NTT's
-// butterflies, the one place where these multiplies are the hot path). Elsewhere nothing here is
-// hot: ~31 multiplies per twiddle against the 254 point doublings the twiddle then drives.
+// butterflies, and eval_kernels.hip: the batch inversion and the division in evaluation form, the
+// places where these multiplies are the hot path; evals.hip starts that division from
+// fr_eval_setup). Elsewhere nothing here is hot: ~31 multiplies per twiddle against the 254 point
+// doublings the twiddle then drives.
 //
 // Plain C++17 unless the compiler is hipcc, so a host program can include this file alone
-// (tests/host_units/fr_units.cpp, built by g++ with and without sanitizers).
+// (tests/host_units/fr_units.cpp and eval_units.cpp, built by g++ with and without sanitizers).
 #pragma once
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
@@ -213,6 +215,117 @@ KZG_HD void fr_fill_powers(fr (&p)[N], fr x) {
     p[k] = x;
     fr_mul(x, x, x);
   }
+}
+
+// ---------------------------------------------------------------- evaluation form (evals.hip)
+KZG_HD bool fr_is_zero(const fr& a) {
+  uint32_t any = 0;
+  for (int i = 0; i < 8; i++) any |= a.v[i];
+  return any == 0;
+}
+// The inverse of a (Montgomery form in and out; 0 for 0) without a multiplication: Kaliski's almost
+// inverse ("The Montgomery inverse and its applications", 1995), then doublings; 512 steps in all
+// whatever a is. The binary steps work on u, v, r, s from (the modulus, a, 0, 1) and keep
+// u s + v r = the modulus, so s <= the modulus while u >= 1 and r <= the modulus while v >= 1, and
+// the step that leaves v = 0 doubles r once more: every value stays below 2^256 (the modulus has 255
+// bits). After those k steps (255 <= k <= 510) the modulus minus r is a^-1 2^k, and the remaining
+// 512 - k steps double it: a^-1 2^512 = a^-1 R^2 is the Montgomery form of the inverse of the value
+// that a stands for. A step is a few word-wide shifts, one comparison and one addition or
+// subtraction; fr_inv's ladder is 383 multiplications.
+KZG_HD fr fr_inv_binary(const fr& a) {
+  uint32_t u[8], v[8], r[8], s[8];
+  for (int i = 0; i < 8; i++) u[i] = FR_R[i], v[i] = a.v[i], r[i] = 0, s[i] = i == 0;
+  fr x = {{0, 0, 0, 0, 0, 0, 0, 0}};
+  bool reduced = fr_is_zero(a);  // x holds a^-1 2^(steps so far)
+  auto halve = [](uint32_t (&w)[8]) {
+    for (int i = 0; i < 8; i++) w[i] = (w[i] >> 1) | (i < 7 ? w[i + 1] << 31 : 0u);
+  };
+  auto twice = [](uint32_t (&w)[8]) {
+    for (int i = 7; i >= 0; i--) w[i] = (w[i] << 1) | (i > 0 ? w[i - 1] >> 31 : 0u);
+  };
+  auto add = [](uint32_t (&w)[8], const uint32_t (&y)[8]) {  // below 2^256: no carry out
+    uint64_t c = 0;
+    for (int i = 0; i < 8; i++) {
+      c += (uint64_t)w[i] + y[i];
+      w[i] = (uint32_t)c;
+      c >>= 32;
+    }
+  };
+  auto sub = [](uint32_t (&w)[8], const uint32_t (&y)[8]) -> bool {  // w -= y; true: it wrapped (w < y)
+    uint32_t br = 0;
+    for (int i = 0; i < 8; i++) {
+      const uint64_t d = (uint64_t)w[i] - y[i] - br;
+      w[i] = (uint32_t)d;
+      br = (uint32_t)(d >> 32) & 1u;
+    }
+    return br != 0;
+  };
+#ifdef __HIP_DEVICE_COMPILE__
+#pragma unroll 1
+#endif
+  for (int step = 0; step < 512; step++) {
+    if (reduced) {
+      fr_add(x, x, x);
+      continue;
+    }
+    if (!(u[0] & 1)) {
+      halve(u), twice(s);
+    } else if (!(v[0] & 1)) {
+      halve(v), twice(r);
+    } else {
+      uint32_t d[8];
+      for (int i = 0; i < 8; i++) d[i] = u[i];
+      if (!sub(d, v)) {  // u >= v; equal only when both are 1, the last step
+        bool zero = true;
+        for (int i = 0; i < 8; i++) zero = zero && d[i] == 0;
+        if (zero) {  // v - u = 0
+          for (int i = 0; i < 8; i++) v[i] = 0;
+          add(s, r), twice(r);
+        } else {
+          for (int i = 0; i < 8; i++) u[i] = d[i];
+          halve(u), add(r, s), twice(s);
+        }
+      } else {
+        sub(v, u);
+        halve(v), add(s, r), twice(r);
+      }
+    }
+    bool done = true;
+    for (int i = 0; i < 8; i++) done = done && v[i] == 0;
+    if (done) {  // r < 2 modulus -> the modulus - (r mod modulus)
+      uint32_t t[9];
+      for (int i = 0; i < 8; i++) t[i] = r[i];
+      t[8] = 0;
+      fr rr;
+      fr_cond_sub(rr, t);
+      fr_sub(x, fr{{0, 0, 0, 0, 0, 0, 0, 0}}, rr);
+      reduced = true;
+    }
+  }
+  return x;
+}
+
+// x^(2^k) by k squarings: z^n for the domain of size n = 2^k
+KZG_HD fr fr_pow_2k(fr x, uint32_t k) {
+  for (uint32_t i = 0; i < k; i++) fr_mul(x, x, x);
+  return x;
+}
+// 1 / 2^exp, exp < 64
+KZG_HD fr fr_inv_2k(uint32_t exp) { return fr_inv(fr_from_u64((uint64_t)1 << exp)); }
+// What the division in evaluation form reads for the domain of size n = 2^exp <= 2^26 and a point z
+// (any 256-bit integer): pw[k] = w^(2^k) for w = fr_domain_root(exp) (1 from k = exp on), z, and the
+// barycentric factor (z^n - 1) / n, which is zero exactly where z lies on the domain. Montgomery form.
+constexpr int kEvalPowers = 26;
+struct fr_eval_scalars {
+  fr pw[kEvalPowers];
+  fr z, scale;
+};
+KZG_HD void fr_eval_setup(fr_eval_scalars& sc, uint32_t exp, const uint8_t z_le32[32]) {
+  fr_fill_powers(sc.pw, fr_domain_root(exp));
+  sc.z = fr_from_le32(z_le32);
+  fr zn1;
+  fr_sub(zn1, fr_pow_2k(sc.z, exp), fr_one());
+  fr_mul(sc.scale, zn1, fr_inv_2k(exp));
 }
 
 }  // namespace kzgpot

@@ -1,14 +1,15 @@
 // The launch plans of the group FFT (fft_kernels.hip), the multi-scalar multiplication
 // (msm_kernels.hip), the polynomial division (poly_kernels.hip), KZG10 open (open.hip), the Fr NTT
-// (ntt_kernels.hip) and the amortized openings over a domain (domain.hip), each stated once: where
-// every kernel reads and writes inside the caller-supplied workspace, and the launch schedule as
-// data (one entry per stage, level or step, in launch order). The launchers run the tables; nothing
-// else decides an offset or a lane count.
+// (ntt_kernels.hip), the amortized openings over a domain (domain.hip) and the evaluation form
+// (eval_kernels.hip, evals.hip), each stated once: where every kernel reads and writes inside the
+// caller-supplied workspace, and the launch schedule as data (one entry per stage, level or step, in
+// launch order). The launchers run the tables; nothing else decides an offset or a lane count.
 //
 // Plain C++17 with no HIP header, so a host program can include this file alone
 // (tests/host_units/plan_units.cpp, built by g++ with and without sanitizers; tests/test_plan_units.py
 // checks every launch's reads and writes against its regions; tests/host_units/ntt_units.cpp and
-// tests/test_ntt_units.py do the same for the last two plans).
+// tests/test_ntt_units.py do the same for the NTT's and the domain's plans,
+// tests/host_units/eval_units.cpp and tests/test_eval_units.py for the evaluation form's).
 #pragma once
 #include <stdint.h>
 
@@ -285,6 +286,71 @@ inline OpenPlan open_plan(uint64_t n, uint64_t n_blind, uint32_t flags) {
   p.scalars = o, o += align256((p.nq + p.nb) * 32);
   p.values = o, o += 256;
   p.poly = o, o += poly_workspace_bytes(n > n_blind ? n : n_blind, p.t);  // one division at a time
+  p.msm = o, o += msm_bytes;
+  p.bytes = o;
+  p.ok = true;
+  return p;
+}
+
+// ---------------------------------------------------------------- evaluation form (eval_kernels.hip)
+// n = 2^exp evaluations in tiles of 2^t (the division's tiles and flag). Workspace of the division
+// in evaluation form: inv (n entries of 32 B, 1 / (z - w^i) in Montgomery form), sums and qsums (one
+// partial sum of 32 B per tile: the barycentric sum, and the sum behind the quotient's entry m when
+// z = w^m), and 256 B of words: the index m at byte 0 (a 32-bit word, all ones unless z is on the
+// domain) and the value at byte 32 (canonical).
+constexpr uint32_t kEvalMaxExp = 26;
+constexpr uint64_t kEvalMaxN = (uint64_t)1 << kEvalMaxExp;  // of the batch inversion too
+constexpr uint32_t kEvalNoIndex = ~0u;
+constexpr uint64_t kEvalValueAt = 32;  // inside the words region
+struct EvalPlan {
+  uint32_t exp, t;
+  uint64_t n, tiles;
+  uint64_t inv, sums, qsums, words, bytes;  // byte offsets; bytes = 0: invalid arguments
+};
+inline EvalPlan eval_plan(uint32_t exp, uint32_t t) {
+  EvalPlan p = {};
+  if (exp > kEvalMaxExp || t < kPolyTileMin || t > kPolyTileMax) return p;
+  p.exp = exp, p.t = t;
+  p.n = (uint64_t)1 << exp;
+  p.tiles = (p.n + ((uint64_t)1 << t) - 1) >> t;
+  uint64_t o = 0;
+  p.inv = o, o += align256(p.n * 32);
+  p.sums = o, o += align256(p.tiles * 32);
+  p.qsums = o, o += align256(p.tiles * 32);
+  p.words = o, o += 256;
+  p.bytes = o;
+  return p;
+}
+inline uint64_t eval_workspace_bytes(uint32_t exp, uint32_t flags) {
+  uint32_t t;
+  return poly_flags(flags, t) ? eval_plan(exp, t).bytes : 0;
+}
+// tiles of a batch inversion of n entries; 0: invalid arguments or nothing to do
+inline uint64_t batch_inverse_tiles(uint64_t n, uint32_t t) {
+  if (n > kEvalMaxN || t < kPolyTileMin || t > kPolyTileMax) return 0;
+  return (n + ((uint64_t)1 << t) - 1) >> t;
+}
+
+// KZG10 open from evaluations: the division's workspace, the quotient's n evaluations (the one
+// MSM's scalars; its bases are the caller's Lagrange records where they lie), the MSM's workspace.
+struct OpenEvalsPlan {
+  EvalPlan ev;
+  uint32_t c;  // the width override, 0 for the library's
+  uint64_t rec;
+  uint64_t quot, msm, bytes;  // byte offsets (the division's workspace is at 0)
+  bool ok;
+};
+inline OpenEvalsPlan open_evals_plan(uint32_t exp, uint32_t flags) {
+  OpenEvalsPlan p = {};
+  uint32_t t;
+  if (!open_flags(flags, t, p.c)) return p;
+  p.ev = eval_plan(exp, t);
+  if (!p.ev.bytes) return p;
+  const uint64_t msm_bytes = msm_workspace_bytes(false, p.ev.n, p.c);
+  if (!msm_bytes) return p;
+  p.rec = base_record(false, flags & KZGPOT_MSM_BASES_MONT);
+  uint64_t o = p.ev.bytes;
+  p.quot = o, o += align256(p.ev.n * 32);
   p.msm = o, o += msm_bytes;
   p.bytes = o;
   p.ok = true;

@@ -22,7 +22,8 @@
 // loop's trip count is a compile-time constant. No lane does more than 2 M <= 32 Horner steps and
 // 8 scan steps. Evaluate-only (no quotient) runs the up passes and the top level's down pass alone.
 //
-// Memory: a lane's run is M x 32 B at a stride of M x 32 B, so tiles are staged through LDS: every
+// Memory (the tile and its helpers are poly_parts.hpp's, shared with eval_kernels.hip): a lane's run
+// is M x 32 B at a stride of M x 32 B, so tiles are staged through LDS: every
 // global load and store is one uint4 per lane at consecutive addresses, and a lane reads its run
 // from LDS at a stride of 2 M + 1 uint4 (one uint4 of padding per run: an odd stride, so the 16-byte
 // reads of neighbouring lanes fall into different banks). Level 0 reads 32 B per coefficient in
@@ -38,6 +39,7 @@
 #include <stdint.h>
 
 #include "codec.hpp"
+#include "poly_parts.hpp"
 
 namespace kzgpot {
 namespace {
@@ -46,50 +48,6 @@ namespace {
 struct PolyPowers {
   fr p[kPolyTileMax];
 };
-
-template <int T>
-struct Tile {
-  static constexpr int S = 1 << T, M = S / 256, RUN = 2 * M + 1;  // RUN: uint4 per lane, padded
-  static constexpr int SLOTS = 256 * RUN;
-  static constexpr int LOG2M = T - 8;
-};
-
-__device__ inline void tile_get(fr& a, const uint4* tile, int slot) {
-  const uint4 lo = tile[slot], hi = tile[slot + 1];
-  a.v[0] = lo.x, a.v[1] = lo.y, a.v[2] = lo.z, a.v[3] = lo.w;
-  a.v[4] = hi.x, a.v[5] = hi.y, a.v[6] = hi.z, a.v[7] = hi.w;
-}
-__device__ inline void tile_put(uint4* tile, int slot, const fr& a) {
-  tile[slot] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
-  tile[slot + 1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
-// a lane's column of the 256 run sums (word-major: neighbouring lanes, neighbouring banks)
-__device__ inline void park(uint32_t (*rows)[256], uint32_t lane, const fr& a) {
-#pragma unroll
-  for (int k = 0; k < 8; k++) rows[k][lane] = a.v[k];
-}
-__device__ inline void unpark(fr& a, const uint32_t (*rows)[256], uint32_t lane) {
-#pragma unroll
-  for (int k = 0; k < 8; k++) a.v[k] = rows[k][lane];
-}
-__device__ inline void mul_add(fr& acc, const fr& x, const fr& y, const fr& c) {  // acc = x y + c
-  fr t;
-  fr_mul(t, x, y);
-  fr_add(acc, t, c);
-}
-
-// entries [blk S, (blk + 1) S) of `in` (n_in entries of 32 B; zero past the end) -> the padded tile
-template <int T>
-__device__ inline void stage_in(uint4* tile, const uint4* in, uint64_t blk, uint64_t n_in) {
-  using G = Tile<T>;
-  const uint64_t base = blk * (2 * G::S), end = 2 * n_in;
-#pragma unroll
-  for (int r = 0; r < 2 * G::M; r++) {
-    const int i = r * 256 + (int)threadIdx.x;
-    const uint64_t g = base + (uint64_t)i;
-    tile[i + (i >> (G::LOG2M + 1))] = g < end ? in[g] : make_uint4(0, 0, 0, 0);
-  }
-}
 
 // the lane's run sum: sum_k c[k] z^k over its M entries. Level 0 (raw) converts each entry to
 // Montgomery form and leaves it converted in the tile.

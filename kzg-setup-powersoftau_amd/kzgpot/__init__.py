@@ -771,3 +771,99 @@ def kzg_open_domain(table, coeffs, exp: int, g2: bool = False, tile: int = 0, wa
     cut = (192 if g2 else 96) << exp
     values = [int.from_bytes(out[o: o + 32], "little") for o in range(cut, len(out), 32)] if want_values else None
     return DomainProofs(out[:cut], values)
+
+
+# ------------------------------------------------------------------ evaluation form: batch inversion, KZG10 open
+EVALS_MAX_EXP = 26
+
+
+def fr_batch_inverse(values, tile: int = 0) -> bytes:
+    """out[i] = values[i]^-1 mod r, and 0 where values[i] = 0 mod r (ark-ff's `batch_inversion`), on
+    the GPU. `values` are 32-byte little-endian integers (bytes-like) or Python ints in [0, 2^256),
+    each reduced mod r; returns as many canonical 32-byte little-endian values."""
+    data = _scalar_bytes(values)
+    if len(data) % 32:
+        raise ValueError(f"fr_batch_inverse: {len(data)} B of values")
+    out = ctypes.create_string_buffer(max(1, len(data)))
+    r = _lib.load().kzgpot_fr_batch_inverse(data, len(data) // 32, out, poly_flags(tile))
+    if r:
+        raise KzgPotError(r)
+    return out.raw[: len(data)]
+
+
+def fr_evals_workspace(exp: int, flags: int = 0) -> int:
+    return int(_lib.load().kzgpot_fr_evals_workspace(exp, flags))
+
+
+def kzg_open_evals_workspace(exp: int, flags: int = 0) -> int:
+    return int(_lib.load().kzgpot_kzg_open_evals_workspace(exp, flags))
+
+
+def _evals_bytes(evals, exp: int, what: str) -> bytes:
+    data = _scalar_bytes(evals)
+    if not 0 <= exp <= EVALS_MAX_EXP or len(data) != 32 << exp:
+        raise ValueError(f"{what}: {len(data)} B for 2^{exp} evaluations")
+    return data
+
+
+def fr_evals_divide(evals, exp: int, z, tile: int = 0, want_quotient: bool = True):
+    """(quotient_bytes, value) of the division by (x - z) in evaluation form on the GPU: `evals` are
+    the 2^exp values p(w^i) of a polynomial of degree below 2^exp, natural order, w =
+    fr_domain_root(exp); value = p(z) as an int below r, quotient_bytes the 2^exp canonical 32-byte
+    little-endian values of (p(x) - p(z)) / (x - z) at the same points. z may lie on the domain.
+    `evals` (bytes-like or Python ints) and `z` are reduced mod r."""
+    data = _evals_bytes(evals, exp, "fr_evals_divide")
+    quot = ctypes.create_string_buffer(len(data)) if want_quotient else None
+    value = ctypes.create_string_buffer(32)
+    r = _lib.load().kzgpot_fr_evals_divide(data, exp, _fr_bytes(z), quot, value, poly_flags(tile))
+    if r:
+        raise KzgPotError(r)
+    return (quot.raw if want_quotient else None), int.from_bytes(value.raw, "little")
+
+
+def kzg_evaluate_evals(evals, exp: int, z) -> int:
+    """p(z) mod r from the evaluations of p over the domain of size 2^exp (the barycentric formula)."""
+    return fr_evals_divide(evals, exp, z, want_quotient=False)[1]
+
+
+def lagrange_basis(powers_records, exp: int) -> bytes:
+    """[L_i(tau)]G, i < 2^exp, natural order, from the first 2^exp packed ark-uncompressed records
+    [tau^j]G: g1_fft's inverse transform. A malformed record raises KzgPotError with its index."""
+    ptr, nbytes, keep = _buf(powers_records)
+    if not 0 <= exp <= 32 or nbytes < 96 << exp:
+        raise ValueError(f"lagrange_basis: {nbytes} B is less than 2^{exp} records of 96 B")
+    first = ctypes.string_at(ptr, 96 << exp)
+    del keep
+    return _checked(g1_fft(first, exp, inverse=True))
+
+
+def kzg_commit_evals(lagrange, evals) -> bytes:
+    """The commitment to p from its evaluations: sum_i [e_i] lagrange[i], one MSM over packed
+    ark-uncompressed records. Equals kzg_commit over the monomial powers for the coefficients of p."""
+    return _checked(g1_msm(lagrange, evals))
+
+
+def g1_kzg_open_evals(lagrange, evals, exp: int, z, mont: bool = False, window: int = 0, tile: int = 0) -> CodecResult:
+    """kzgpot_g1_kzg_open_evals on packed records: `out` is the 128 bytes w ‖ value; a malformed
+    base gives ret = -(status), first_bad = its index and out = b""."""
+    rec = G1_ARK_MONT_BYTES if mont else 96
+    data = _evals_bytes(evals, exp, "kzg open evals")
+    ptr, nbytes, keep = _buf(lagrange)
+    if nbytes != rec << exp:
+        raise ValueError(f"kzg open evals: {nbytes} B of {rec}-B bases for 2^{exp} evaluations")
+    out = ctypes.create_string_buffer(128)
+    fb = ctypes.c_int64(-1)
+    ret = _lib.load().kzgpot_g1_kzg_open_evals(ptr, data, exp, _fr_bytes(z), out,
+                                               msm_flags(mont, window) | poly_flags(tile), ctypes.byref(fb))
+    del keep
+    if ret <= -100:
+        raise KzgPotError(ret)
+    return CodecResult(out.raw if ret == 0 else b"", ret, fb.value, None)
+
+
+def kzg_open_evals(lagrange, evals, exp: int, z, window: int = 0, tile: int = 0) -> KzgProof:
+    """The KZG10 opening proof of p at z from the 2^exp evaluations of p and lagrange_basis's records:
+    the `w` and `value` kzg_open returns for the coefficients of p, with no inverse NTT and no
+    monomial powers. Not hiding: `random_v` is None. A malformed record raises KzgPotError."""
+    out = _checked(g1_kzg_open_evals(lagrange, evals, exp, z, window=window, tile=tile))
+    return KzgProof(out[:96], None, int.from_bytes(out[96:], "little"))

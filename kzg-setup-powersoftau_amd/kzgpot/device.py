@@ -319,3 +319,67 @@ def g1_open_domain_dev(d_table, d_coeffs, exp, d_proofs, d_values, key, **kw) ->
 
 def g2_open_domain_dev(d_table, d_coeffs, exp, d_proofs, d_values, key, **kw) -> torch.Tensor:
     return open_domain_dev(True, d_table, d_coeffs, exp, d_proofs, d_values, key, **kw)
+
+
+def fr_batch_inverse_dev(d_in: torch.Tensor, d_out: torch.Tensor, tile: int = 0) -> None:
+    """Asynchronous batch inversion on device tensors (torch's current stream): n 32-byte
+    little-endian values in, as many canonical inverses out (0 for a zero); d_out may be d_in."""
+    n = d_in.numel() // 32
+    if d_in.numel() != 32 * n or d_out.numel() < 32 * n:
+        raise ValueError(f"batch inverse: bad buffer sizes {d_in.numel()} / {d_out.numel()}")
+    if not (d_in.is_cuda and d_out.is_cuda):
+        raise ValueError("fr_batch_inverse_dev needs device tensors")
+    rc = _lib.load().kzgpot_fr_batch_inverse_dev(d_in.data_ptr() if n else None, n, d_out.data_ptr() if n else None,
+                                                 tile << 16, _stream())
+    if rc:
+        raise RuntimeError(f"batch inverse: launch failed ({rc})")
+
+
+def fr_evals_divide_dev(d_evals: torch.Tensor, exp: int, z: int, d_quotient: torch.Tensor | None, d_value: torch.Tensor,
+                        tile: int = 0, work: torch.Tensor | None = None) -> torch.Tensor:
+    """Asynchronous division by (x - z) in evaluation form on device tensors (torch's current
+    stream): 2^exp 32-byte evaluations in, as many quotient evaluations (None: evaluate only) and
+    the 32-byte value out. Allocates the workspace (kzgpot_fr_evals_workspace bytes) unless `work`
+    is given; returns it — keep it alive until the stream has run the call."""
+    if (d_evals.numel() != 32 << exp or d_value.numel() < 32
+            or (d_quotient is not None and d_quotient.numel() < 32 << exp)):
+        raise ValueError(f"evals divide: bad buffer sizes {d_evals.numel()} / {d_value.numel()}")
+    if not (d_evals.is_cuda and d_value.is_cuda and (d_quotient is None or d_quotient.is_cuda)):
+        raise ValueError("fr_evals_divide_dev needs device tensors")
+    lib = _lib.load()
+    flags = tile << 16
+    need = int(lib.kzgpot_fr_evals_workspace(exp, flags))
+    if need == 0:
+        raise ValueError(f"evals divide: exp = {exp} with tile {tile} is not supported")
+    work = _work(need, work, d_value.device, "evals divide")
+    rc = lib.kzgpot_fr_evals_divide_dev(d_evals.data_ptr(), exp, int(z).to_bytes(32, "little"),
+                                        d_quotient.data_ptr() if d_quotient is not None else None, d_value.data_ptr(),
+                                        flags, work.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"evals divide: launch failed ({rc})")
+    return work
+
+
+def g1_kzg_open_evals_dev(d_lagrange: torch.Tensor, d_evals: torch.Tensor, exp: int, z: int, d_out: torch.Tensor,
+                          key: torch.Tensor, mont: bool = False, window: int = 0, tile: int = 0,
+                          work: torch.Tensor | None = None) -> torch.Tensor:
+    """Asynchronous KZG10 open from evaluations on device tensors (torch's current stream): the
+    2^exp Lagrange-basis records and evaluations in, 128 bytes (w ‖ value) into d_out. Allocates the
+    workspace (kzgpot_kzg_open_evals_workspace bytes) unless `work` is given; returns it — keep it
+    alive until the stream has run the call."""
+    rec = 104 if mont else 96
+    if d_lagrange.numel() != rec << exp or d_evals.numel() != 32 << exp or d_out.numel() < 128:
+        raise ValueError(f"kzg open evals: bad buffer sizes {d_lagrange.numel()} / {d_evals.numel()} / {d_out.numel()}")
+    if not all(t.is_cuda for t in (d_lagrange, d_evals, d_out, key)):
+        raise ValueError("g1_kzg_open_evals_dev needs device tensors")
+    lib = _lib.load()
+    flags = (1 if mont else 0) | (window << 8) | (tile << 16)
+    need = int(lib.kzgpot_kzg_open_evals_workspace(exp, flags))
+    if need == 0:
+        raise ValueError(f"kzg open evals: exp = {exp} with window {window}, tile {tile} is not supported")
+    work = _work(need, work, d_out.device, "kzg open evals")
+    rc = lib.kzgpot_g1_kzg_open_evals_dev(d_lagrange.data_ptr(), d_evals.data_ptr(), exp, int(z).to_bytes(32, "little"),
+                                          d_out.data_ptr(), flags, work.data_ptr(), key.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"kzg open evals: launch failed ({rc})")
+    return work
