@@ -66,9 +66,16 @@ KZG_DEV void fp_zero(Fe<Tr>& r) {
 }
 
 // 2x as a VOP2 add: a wave64 v_add_u32 issues in ~2 SIMD cycles, the v_lshlrev_b32 the compiler
-// emits for x << 1 in ~4 (profiles/r02_valu_issue_microbench.txt). asm, or the compiler folds it back.
+// emits for x << 1 in ~4 (profiles/r02_valu_issue_microbench.txt). asm, or the compiler folds it back
+// (x + x too). Both cores double through these: the 14 x 28 limbs with dbl_u32, the radix-2^30 core's
+// signed digits with dbl_i32 — the same instruction, the same 32 bits as x + x.
 KZG_DEV uint32_t dbl_u32(uint32_t x) {
   uint32_t r;
+  asm("v_add_u32_e32 %0, %1, %1" : "=v"(r) : "v"(x));
+  return r;
+}
+KZG_DEV int32_t dbl_i32(int32_t x) {
+  int32_t r;
   asm("v_add_u32_e32 %0, %1, %1" : "=v"(r) : "v"(x));
   return r;
 }
@@ -548,11 +555,47 @@ struct f30 {
 };
 KZG_DEV int32_t sext30(uint32_t x) { return __builtin_amdgcn_sbfe((int32_t)x, 0, 30); }
 
+// a b + c as one opaque v_mad_i64_i32 (its carry-out goes to a scratch SGPR pair): a chain of these
+// cannot be re-associated by the compiler. mad_i64_chain_k: b a wave-uniform constant in an SGPR (a
+// digit of p).
+KZG_DEV int64_t mad_i64_chain(int32_t a, int32_t b, int64_t c) {
+  int64_t r;
+  uint64_t carry_out;
+  asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry_out) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+KZG_DEV int64_t mad_i64_chain_k(int32_t a, int32_t k, int64_t c) {
+  int64_t r;
+  uint64_t carry_out;
+  asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry_out) : "v"(a), "s"(k), "v"(c));
+  return r;
+}
+// c + a b, c + a k on one accumulator. Chain = true: through the opaque mads above, so that a column is
+// ONE serial chain on the running carry and costs no 64-bit merge at all; left to itself the compiler
+// splits every column into two or three chains and merges them (v_lshl_add_u64, an instruction like
+// any other to a kernel bound by VALU issue). The price is an s_nop between dependent asm mads
+// (~1,360 per ladder doubling), which a second wave on the SIMD hides: the G1 codec, at 2 waves per SIMD
+// on every launch that matters, runs Chain = true; the G2 codec, whose 2^16-point launches put one wave
+// on a SIMD, keeps the compiler's chains (profiles/r10_ab_f30_serial.json).
+template <bool Chain>
+KZG_DEV int64_t f30_mac(int32_t a, int32_t b, int64_t c) {
+  if constexpr (Chain) return mad_i64_chain(a, b, c);
+  else return c + (int64_t)a * b;
+}
+template <bool Chain>
+KZG_DEV int64_t f30_mac_k(int32_t a, int32_t k, int64_t c) {
+  if constexpr (Chain) return mad_i64_chain_k(a, k, c);
+  else return c + (int64_t)a * k;
+}
 // r = a b 2^-390 mod p for balanced a, b (|digit| <= 2^29, |top digit| <= 2^23: the bound
 // tests/test_fp30.py proves, TOP_IN = 2^23 + 1, and the exponentiation's callers use); r balanced with
 // |value| < p/2 + |a| |b| / R30. The lower columns are made divisible by 2^30 by m_i = balanced
-// (col * PINV30); the upper columns start their a*b partial sum at +2^29, so that the digit
-// (acc & M30) - 2^29 and the carry acc >> 30 are the balanced remainder and its exact quotient.
+// (col * PINV30); an upper column's digit is the balanced remainder of its sum (one v_bfe_i32) and its
+// carry (acc + 2^29) >> 30 the exact quotient — the same integers as the biased form of
+// tests/test_fp30.py (the sum started at +2^29, digit (acc & M30) - 2^29, carry acc >> 30), an
+// instruction fewer per column where the bias is no chain's free start addend. Every partial sum is
+// bounded by the sum of absolute values those tests prove, in any order of accumulation.
+template <bool Chain = true>
 KZG_DEV void f30_mul(f30& r, const f30& a, const f30& b) {
   KZG_FPOP(FpOp::Mul30);
   constexpr int N = N30;
@@ -562,64 +605,52 @@ KZG_DEV void f30_mul(f30& r, const f30& a, const f30& b) {
   for (int i = 0; i < 2 * N - 1; i++) {
     const int j0 = i < N ? 0 : i - (N - 1);
     const int j1 = i < N ? i - 1 : N - 1;
-    int64_t accab = i < N ? 0 : (int64_t)1 << 29, accp = 0;
 #pragma unroll
     for (int j = j0; j <= j1; j++) {
-      accab += (int64_t)a.v[j] * b.v[i - j];
-      accp += (int64_t)m[j] * P30[i - j];
+      acc = f30_mac<Chain>(a.v[j], b.v[i - j], acc);
+      acc = f30_mac_k<Chain>(m[j], P30[i - j], acc);
     }
-    acc += accab;
     if (i < N) {
-      acc += (int64_t)a.v[i] * b.v[0];
-      acc += accp;
+      acc = f30_mac<Chain>(a.v[i], b.v[0], acc);
       m[i] = sext30((uint32_t)acc * PINV30);
       acc += (int64_t)m[i] * P30[0];
     } else {
-      acc += accp;
-      r.v[i - N] = (int32_t)((uint32_t)acc & ((1u << 30) - 1)) - (1 << 29);
+      r.v[i - N] = sext30((uint32_t)acc);
+      acc += (int64_t)1 << 29;
     }
     acc >>= 30;
   }
   r.v[N - 1] = (int32_t)acc;
 }
-// a b + c as one opaque v_mad_i64_i32 (its carry-out goes to a scratch SGPR pair): a chain of these
-// cannot be re-associated by the compiler
-KZG_DEV int64_t mad_i64_chain(int32_t a, int32_t b, int64_t c) {
-  int64_t r;
-  uint64_t carry_out;
-  asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry_out) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
 // r = a^2 2^-390: cross products once as a_j (2 a_k), the same reduction. The upper columns chain
-// their a*d products onto the incoming carry (mad_i64_chain), one 64-bit merge fewer per column than
-// the compiler's re-associated sums: 94.5 against 92.6 G squarings/s (profiles/r03o_mont30_chained.txt;
-// the same chaining made the multiply 1.3 % slower, so f30_mul keeps the compiler's form).
+// their a*d products onto the incoming carry in either form (mad_i64_chain: 94.5 against 92.6 G
+// squarings/s, profiles/r03o_mont30_chained.txt); Chain = true chains the lower columns and the m*p
+// products as well.
+template <bool Chain = true>
 KZG_DEV void f30_sqr(f30& r, const f30& a) {
   KZG_FPOP(FpOp::Sqr30);
   constexpr int N = N30;
   int32_t d[N], m[N];
 #pragma unroll
-  for (int j = 0; j < N; j++) d[j] = a.v[j] + a.v[j];
+  for (int j = 0; j < N; j++) d[j] = dbl_i32(a.v[j]);
   int64_t acc = 0;
 #pragma unroll
   for (int i = 0; i < 2 * N - 1; i++) {
     const int j0 = i < N ? 0 : i - (N - 1);
     const int k1 = i < N ? i - 1 : N - 1;
-    int64_t accp = 0;
-    if (i >= N) acc += (int64_t)1 << 29;
 #pragma unroll
     for (int j = j0; 2 * j < i; j++)
-      acc = i >= N ? mad_i64_chain(a.v[j], d[i - j], acc) : acc + (int64_t)a.v[j] * d[i - j];
+      acc = i >= N ? mad_i64_chain(a.v[j], d[i - j], acc) : f30_mac<Chain>(a.v[j], d[i - j], acc);
     if ((i & 1) == 0)
-      acc = i >= N ? mad_i64_chain(a.v[i / 2], a.v[i / 2], acc) : acc + (int64_t)a.v[i / 2] * a.v[i / 2];
+      acc = i >= N ? mad_i64_chain(a.v[i / 2], a.v[i / 2], acc) : f30_mac<Chain>(a.v[i / 2], a.v[i / 2], acc);
 #pragma unroll
-    for (int k = j0; k <= k1; k++) accp += (int64_t)m[k] * P30[i - k];
-    acc += accp;
+    for (int k = j0; k <= k1; k++) acc = f30_mac_k<Chain>(m[k], P30[i - k], acc);
     if (i < N) {
       m[i] = sext30((uint32_t)acc * PINV30);
       acc += (int64_t)m[i] * P30[0];
     } else {
-      r.v[i - N] = (int32_t)((uint32_t)acc & ((1u << 30) - 1)) - (1 << 29);
+      r.v[i - N] = sext30((uint32_t)acc);
+      acc += (int64_t)1 << 29;
     }
     acc >>= 30;
   }
@@ -640,23 +671,20 @@ KZG_DEV void f30_mul_sum2(f30& r, const f30& a, const f30& b, const f30& c, cons
   for (int i = 0; i < 2 * N - 1; i++) {
     const int j0 = i < N ? 0 : i - (N - 1);
     const int j1 = i < N ? i - 1 : N - 1;
-    int64_t accab = i < N ? 0 : (int64_t)1 << 29, acc2 = 0, accp = 0;
 #pragma unroll
     for (int j = j0; j <= j1; j++) {
-      accab += (int64_t)a.v[j] * b.v[i - j];
-      acc2 += (int64_t)c.v[j] * d.v[i - j];
-      accp += (int64_t)m[j] * P30[i - j];
+      acc += (int64_t)a.v[j] * b.v[i - j];
+      acc += (int64_t)c.v[j] * d.v[i - j];
+      acc += (int64_t)m[j] * P30[i - j];
     }
-    acc += accab;
     if (i < N) {
       acc += (int64_t)a.v[i] * b.v[0];
-      acc2 += (int64_t)c.v[i] * d.v[0];
-      acc += acc2 + accp;
+      acc += (int64_t)c.v[i] * d.v[0];
       m[i] = sext30((uint32_t)acc * PINV30);
       acc += (int64_t)m[i] * P30[0];
     } else {
-      acc += acc2 + accp;
-      r.v[i - N] = (int32_t)((uint32_t)acc & ((1u << 30) - 1)) - (1 << 29);
+      r.v[i - N] = sext30((uint32_t)acc);
+      acc += (int64_t)1 << 29;
     }
     acc >>= 30;
   }
@@ -664,35 +692,33 @@ KZG_DEV void f30_mul_sum2(f30& r, const f30& a, const f30& b, const f30& c, cons
 }
 // r = (a b + c^2) 2^-390 mod p, the c^2 half as a squaring (cross products once, as c_j (2 c_k)):
 // the 13-digit form of fp_mul_addsqr<1>, the W-form doubling's -W3 = 2E (X3 - D) + B'^2
+template <bool Chain = true>
 KZG_DEV void f30_mul_addsqr(f30& r, const f30& a, const f30& b, const f30& c) {
   KZG_FPOP(FpOp::Mul30AddSqr);
   constexpr int N = N30;
   int32_t c2[N], m[N];
 #pragma unroll
-  for (int j = 0; j < N; j++) c2[j] = c.v[j] + c.v[j];
+  for (int j = 0; j < N; j++) c2[j] = dbl_i32(c.v[j]);
   int64_t acc = 0;
 #pragma unroll
   for (int i = 0; i < 2 * N - 1; i++) {
     const int j0 = i < N ? 0 : i - (N - 1);
     const int j1 = i < N ? i - 1 : N - 1;
-    int64_t accab = i < N ? 0 : (int64_t)1 << 29, acc2 = 0, accp = 0;
 #pragma unroll
     for (int j = j0; j <= j1; j++) {
-      accab += (int64_t)a.v[j] * b.v[i - j];
-      accp += (int64_t)m[j] * P30[i - j];
+      acc = f30_mac<Chain>(a.v[j], b.v[i - j], acc);
+      acc = f30_mac_k<Chain>(m[j], P30[i - j], acc);
     }
 #pragma unroll
-    for (int j = j0; 2 * j < i; j++) acc2 += (int64_t)c.v[j] * c2[i - j];
-    if ((i & 1) == 0) acc2 += (int64_t)c.v[i / 2] * c.v[i / 2];
-    acc += accab;
+    for (int j = j0; 2 * j < i; j++) acc = f30_mac<Chain>(c.v[j], c2[i - j], acc);
+    if ((i & 1) == 0) acc = f30_mac<Chain>(c.v[i / 2], c.v[i / 2], acc);
     if (i < N) {
-      acc += (int64_t)a.v[i] * b.v[0];
-      acc += acc2 + accp;
+      acc = f30_mac<Chain>(a.v[i], b.v[0], acc);
       m[i] = sext30((uint32_t)acc * PINV30);
       acc += (int64_t)m[i] * P30[0];
     } else {
-      acc += acc2 + accp;
-      r.v[i - N] = (int32_t)((uint32_t)acc & ((1u << 30) - 1)) - (1 << 29);
+      r.v[i - N] = sext30((uint32_t)acc);
+      acc += (int64_t)1 << 29;
     }
     acc >>= 30;
   }
@@ -718,11 +744,11 @@ KZG_DEV void f30_neg(f30& r, const f30& a) {
 }
 KZG_DEV void f30_dbl(f30& r, const f30& a) {
 #pragma unroll
-  for (int i = 0; i < N30; i++) r.v[i] = a.v[i] + a.v[i];
+  for (int i = 0; i < N30; i++) r.v[i] = dbl_i32(a.v[i]);
 }
 KZG_DEV void f30_mul3(f30& r, const f30& a) {
 #pragma unroll
-  for (int i = 0; i < N30; i++) r.v[i] = (a.v[i] << 1) + a.v[i];
+  for (int i = 0; i < N30; i++) r.v[i] = dbl_i32(a.v[i]) + a.v[i];  // two VOP2 adds, not a VOP3 v_lshl_add_u32
 }
 // r = 2^S a with balanced digits, for a digit + 2^(29-S) inside int32 (3 x a product's digit just
 // fits S = 0): digit k of 2^S a splits into its balanced low 30 bits (the sign-extended low 30 - S
@@ -737,10 +763,10 @@ KZG_DEV void f30_norm(f30& r, const f30& a) {
   for (int k = 0; k < N30 - 1; k++) {
     const int32_t lo = __builtin_amdgcn_sbfe(a.v[k], 0, 30 - S);
     const int32_t cn = (a.v[k] + (1 << (29 - S))) >> (30 - S);
-    r.v[k] = S ? (int32_t)((uint32_t)lo << S) + c : lo + c;
+    r.v[k] = S == 1 ? dbl_i32(lo) + c : S ? (int32_t)((uint32_t)lo << S) + c : lo + c;
     c = cn;
   }
-  r.v[N30 - 1] = (int32_t)((uint32_t)a.v[N30 - 1] << S) + c;
+  r.v[N30 - 1] = (S == 1 ? dbl_i32(a.v[N30 - 1]) : (int32_t)((uint32_t)a.v[N30 - 1] << S)) + c;
 }
 // a == 0 (mod p) for any digits and |value| <= K p: a = k p forces k = a_0 p^-1 (mod 2^30), and
 // |k| <= K < 2^29 makes that residue's balanced representative the only candidate — a lane whose
@@ -869,6 +895,7 @@ constexpr bool bls_sqrt_table_is(const int16_t (&e)[8]) {
     if (e[k] != want[k]) return false;
   return true;
 }
+template <bool Chain = true>
 KZG_DEV void fp_pow_pm3d4_30(fp& r, const fp& a_in) {
   typedef uint32_t v8u __attribute__((ext_vector_type(8)));
   static_assert(BlsFp::SQRT_TABLE == 8, "table held as one 8-wide register vector per limb");
@@ -881,26 +908,26 @@ KZG_DEV void fp_pow_pm3d4_30(fp& r, const fp& a_in) {
   f30 a, a2, a4, t, u;
   f30_from_fp(a, a_in);
   put(0, a);              // a
-  f30_sqr(a2, a);         // a^2
-  f30_mul(t, a, a2);      // a^3
+  f30_sqr<Chain>(a2, a);         // a^2
+  f30_mul<Chain>(t, a, a2);      // a^3
   put(1, t);
-  f30_sqr(a4, a2);        // a^4
-  f30_mul(t, t, a4);      // a^7
+  f30_sqr<Chain>(a4, a2);        // a^4
+  f30_mul<Chain>(t, t, a4);      // a^7
   put(2, t);
-  f30_mul(t, t, a2);      // a^9
+  f30_mul<Chain>(t, t, a2);      // a^9
   put(3, t);
-  f30_mul(t, t, a2);      // a^11
+  f30_mul<Chain>(t, t, a2);      // a^11
   put(4, t);
-  f30_mul(t, t, a2);      // a^13
+  f30_mul<Chain>(t, t, a2);      // a^13
   put(5, t);
-  f30_sqr(a4, a4);        // a^8
-  f30_mul(u, t, a4);      // a^21
+  f30_sqr<Chain>(a4, a4);        // a^8
+  f30_mul<Chain>(u, t, a4);      // a^21
   put(6, u);
-  f30_mul(t, t, a2);      // a^15
+  f30_mul<Chain>(t, t, a2);      // a^15
   u = t;
 #pragma unroll 1
-  for (int k = 0; k < 4; k++) f30_sqr(u, u);  // a^240
-  f30_mul(u, u, t);       // a^255
+  for (int k = 0; k < 4; k++) f30_sqr<Chain>(u, u);  // a^240
+  f30_mul<Chain>(u, u, t);       // a^255
   put(7, u);
   f30 acc;
 #pragma unroll
@@ -911,16 +938,16 @@ KZG_DEV void fp_pow_pm3d4_30(fp& r, const fp& a_in) {
     const int nsq = sched_nsq(step), idx = sched_idx(step);
     step = kSqrtSchedule<BlsFp>.step[s + 1];  // in flight during this step's squarings
 #pragma unroll 1
-    for (int k = 0; k < nsq; k++) f30_sqr(acc, acc);
+    for (int k = 0; k < nsq; k++) f30_sqr<Chain>(acc, acc);
     if (idx >= 0) {
 #pragma unroll
       for (int k = 0; k < N30; k++) t.v[k] = (int32_t)tab[k][idx];
-      f30_mul(acc, acc, t);
+      f30_mul<Chain>(acc, acc, t);
     }
   }
 #pragma unroll
   for (int k = 0; k < N30; k++) t.v[k] = POW30_OUT[k];
-  f30_mul(acc, acc, t);
+  f30_mul<Chain>(acc, acc, t);
   fp_from_f30(r, acc);
 }
 
@@ -971,9 +998,9 @@ KZG_DEV void fp_pow_pm3d4_window(Fe<Tr>& r, const Fe<Tr>& a) {
 }
 // a^((p-3)/4) for either field: BLS12-381 on the radix-2^30 core with its own table, BN254 by
 // the sliding window above
-template <class Tr>
+template <bool Chain = true, class Tr>
 KZG_DEV void fp_pow_pm3d4(Fe<Tr>& r, const Fe<Tr>& a) {
-  if constexpr (__is_same(Tr, BlsFp)) fp_pow_pm3d4_30(r, a);
+  if constexpr (__is_same(Tr, BlsFp)) fp_pow_pm3d4_30<Chain>(r, a);
   else fp_pow_pm3d4_window(r, a);
 }
 
