@@ -15,7 +15,10 @@
 //    multiple of p in a "borrowed" limb form whose every limb dominates b's (bls12_381_consts.hpp).
 //    NL VALU instructions, no carry chain, no wait states.
 //
-// Bounds discipline (checked for every formula by tests/test_field_bounds.py): a value is
+// Bounds discipline (checked for every formula by tests/test_field_bounds.py, test_field_bounds_msm.py
+// and test_field_bounds_lagrange.py on intervals; tests/test_gpu_fp28_core.py then runs every function
+// below on the GPU with each limb AT those bounds, limb for limb against the exact integer model
+// tests/fp28_model.py): a value is
 // "normalized" (N) when all limbs < 2^28; fp_mul needs limb-bit(a) + limb-bit(b) <= 60 and returns
 // N with value < p (1 + v(a) v(b) p / R); loose values (limbs up to 2^30-2^32 after a few
 // limb-wise adds) only ever feed fp_mul or a further limb-wise op, never storage-to-bytes or a

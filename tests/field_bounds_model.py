@@ -42,7 +42,8 @@ FIELDS = {  # p, limbs, limb bits, constants header
 
 def use_field(name):
     """Re-point the model at another field (the device code is generic over the traits struct)."""
-    global P, NL, LB, LM, R, P_L, P_OVER_R, P_TOP, C
+    global P, NL, LB, LM, R, P_L, P_OVER_R, P_TOP, C, _FIELD
+    _FIELD = name
     P, NL, LB, hdr = FIELDS[name]
     LM = (1 << LB) - 1
     R = 1 << (LB * NL)
@@ -59,6 +60,19 @@ class BoundError(AssertionError):
 UP = 1.0 + 1e-9  # upward nudge for float value bounds
 P_OVER_R = P / R * UP
 P_TOP = P / (1 << (LB * (NL - 1))) * UP  # p / 2^364
+
+
+# Recorder (off by default; tests/test_gpu_fp28_core.py switches it on): each multiply form stores the
+# limb bounds of its operands, so that a value-level test can drive the device function with every limb
+# AT the bound the proof claims. RECORD = None, or a dict (field, form, name) -> set of operand-bound
+# tuples (one tuple of NL limb bounds per operand).
+RECORD = None
+_FIELD = "bls12_381"
+
+
+def _record(form, name, *operands):
+    if RECORD is not None:
+        RECORD.setdefault((_FIELD, form, name), set()).add(tuple(tuple(v.limbs) for v in operands))
 
 
 class V:
@@ -95,6 +109,7 @@ def mont_output(val):
 
 def mul(a: V, b: V, name="mul"):
     """fp_mul: FIPS with one 64-bit accumulator per column (+ the m*p chain merged in)."""
+    _record("mul", name, a, b)
     carry = 0
     for i in range(2 * NL):
         j0 = 0 if i < NL else i - (NL - 1)
@@ -112,6 +127,7 @@ def mul(a: V, b: V, name="mul"):
 
 def mul_sum2(a: V, b: V, c: V, d: V, name="mul_sum2"):
     """fp_mul_sum2: a b + c d with one Montgomery reduction (three mad chains per column)."""
+    _record("mul_sum2", name, a, b, c, d)
     carry = 0
     for i in range(2 * NL):
         j0 = 0 if i < NL else i - (NL - 1)
@@ -127,6 +143,7 @@ def mul_sum2(a: V, b: V, c: V, d: V, name="mul_sum2"):
 
 def mul_sum3(a: V, b: V, c: V, d: V, e: V, f: V, name="mul_sum3"):
     """fp_mul_sum3: a b + c d + e f with one Montgomery reduction (four mad chains per column)."""
+    _record("mul_sum3", name, a, b, c, d, e, f)
     carry = 0
     for i in range(2 * NL):
         j0 = 0 if i < NL else i - (NL - 1)
@@ -144,6 +161,7 @@ def mul_sum3(a: V, b: V, c: V, d: V, e: V, f: V, name="mul_sum3"):
 def mul_add8sqr(a: V, b: V, c: V, name="mul_add8sqr"):
     """fp_mul_add8sqr: a b + 8 c^2 with one reduction; the c^2 half as a squaring (cross products
     c_j (16 c_k) once, squares c_j (8 c_j)), whose column sums equal those of c (8 c)."""
+    _record("mul_add8sqr", name, a, b, c)
     if max(c.limbs) << 4 >= 1 << 32:
         raise BoundError(f"{name}: 16 c_k must fit 32 bits ({c!r})")
     c8 = V([x << 3 for x in c.limbs], c.val * 8 * UP, name + ".8c")
@@ -163,6 +181,7 @@ def mul_add8sqr(a: V, b: V, c: V, name="mul_add8sqr"):
 def mul_addsqr(a: V, b: V, c: V, name="mul_addsqr"):
     """fp_mul_addsqr<1>: a b + c^2 with one reduction, the c^2 half as a squaring (cross products
     c_j (2 c_k) once, squares c_j c_j): column sums equal those of a b + c c."""
+    _record("mul_addsqr", name, a, b, c)
     if max(c.limbs) << 1 >= 1 << 32:
         raise BoundError(f"{name}: 2 c_k must fit 32 bits ({c!r})")
     carry = 0
@@ -182,7 +201,8 @@ def sqr(a: V, name="sqr"):
     """fp_sqr: same column sums as mul(a, a); the doubled operand 2 a_k must fit 32 bits."""
     if max(a.limbs) >= 1 << 31:
         raise BoundError(f"{name}: squaring input limb >= 2^31 ({a!r})")
-    return mul(a, a, name)
+    _record("sqr", name, a)
+    return mul(a, a, name)  # recorded as a mul site too: the squaring's column bound IS mul(a, a)'s
 
 
 def add_nr(a, b, name="add"):

@@ -8,52 +8,14 @@ import random
 
 import pytest
 
-P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
-N, LB = 14, 28
-MASK = (1 << LB) - 1
-PL = [(P >> (LB * i)) & MASK for i in range(N)]
-PINV = (-pow(P, -1, 1 << LB)) % (1 << LB)
-R = 1 << (LB * N)
+from fp28_model import BLS, mul_addsqr
 
-
-def u64(x, what):
-    if not 0 <= x < 1 << 64:
-        raise OverflowError(f"{what}: {x:#x} leaves uint64")
-    return x
+# the column scan is stated once, in tests/fp28_model.py (all six multiply forms, both fields)
+P, N, LB, MASK, R, val = BLS.p, BLS.NL, BLS.LB, BLS.MASK, BLS.R, BLS.val
 
 
 def mul_add8sqr(a, b, c, scale=8):
-    c8 = [x * scale for x in c]
-    c16 = [x * 2 * scale for x in c]
-    assert all(x < 1 << 32 for x in c16)
-    m, r, acc = [0] * N, [0] * N, 0
-    for i in range(2 * N):
-        j0 = 0 if i < N else i - (N - 1)
-        j1 = i - 1 if i < N else N - 1
-        acc2 = accp = 0
-        for j in range(j0, j1 + 1):
-            acc = u64(acc + a[j] * b[i - j], "acc")
-            accp = u64(accp + m[j] * PL[i - j], "accp")
-        for j in range(j0, i):
-            if 2 * j < i and i - j < N:
-                acc2 = u64(acc2 + c[j] * c16[i - j], "acc2")
-        if i % 2 == 0 and i // 2 < N:
-            acc2 = u64(acc2 + c[i // 2] * c8[i // 2], "acc2")
-        if i < N:
-            acc = u64(acc + a[i] * b[0], "acc")
-            acc = u64(acc + acc2 + accp, "acc")
-            m[i] = ((acc & 0xFFFFFFFF) * PINV) & MASK
-            acc = u64(acc + m[i] * PL[0], "acc")
-            assert acc & MASK == 0
-        else:
-            acc = u64(acc + acc2 + accp, "acc")
-            r[i - N] = acc & MASK
-        acc >>= LB
-    return r
-
-
-def val(limbs):
-    return sum(x << (LB * k) for k, x in enumerate(limbs))
+    return mul_addsqr(BLS, a, b, c, scale)
 
 
 def rand_limbs(rng, limb_max, top_max):
