@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(kBlock) k_f30_op(long n, const int32_t* __rest
   if (arity(OP) >= 2) f30_load(y, b, i);
   if (arity(OP) >= 3) f30_load(z, c, i);
   if (arity(OP) >= 4) f30_load(w, d, i);
-  // the serial-chain forms (the G1 codec's) and, _C, the compiler's chains (the G2 codec's square root)
+  // the serial-chain forms (the codecs') and, _C, the compiler's chains
   if (OP == KZGPOT_F30_MUL) f30_mul<true>(o, x, y);
   if (OP == KZGPOT_F30_SQR) f30_sqr<true>(o, x);
   if (OP == KZGPOT_F30_MUL_ADDSQR) f30_mul_addsqr<true>(o, x, y, z);

@@ -573,13 +573,101 @@ KZG_DEV int64_t mad_i64_chain_k(int32_t a, int32_t k, int64_t c) {
   asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry_out) : "v"(a), "s"(k), "v"(c));
   return r;
 }
+// Blocks: a run of dependent mads on ONE accumulator as ONE asm statement. The compiler's hazard
+// recogniser pads between two asm statements that define the same register (here the carry-out pair: one
+// s_nop 0 per statement) and pads nothing inside a statement, and back-to-back dependent
+// v_mad_i64_i32 need no wait state. The accumulator is tied in and out; the carry-out pair is
+// EARLY-CLOBBER, since the first mad writes it before the later ones have read their digit of p from
+// an SGPR. gfx9 VOP3 takes no literal and one SGPR source, so a digit of p is an "s" operand, one per
+// mad; a statement takes 30 operands, so a run holds at most 13 products (28) or 7 a b / m p pairs (30).
+#define KZG_F30_VV(k) "v_mad_i64_i32 %[c], %[o], %[x" #k "], %[y" #k "], %[c]\n\t"
+#define KZG_F30_VK(k) "v_mad_i64_i32 %[c], %[o], %[m" #k "], %[p" #k "], %[c]\n\t"
+#define KZG_F30_PR(k) KZG_F30_VV(k) KZG_F30_VK(k)
+#define KZG_F30_VV_IN(k) [x##k] "v"(x[k]), [y##k] "v"(y[k])
+#define KZG_F30_VK_IN(k) [m##k] "v"(m[k]), [p##k] "s"(p[k])
+#define KZG_F30_PR_IN(k) KZG_F30_VV_IN(k), KZG_F30_VK_IN(k)
+// KZG_F30_Sn(M): M(0) ... M(n-1) side by side (the string); KZG_F30_Ln(M): comma-separated (the operands)
+#define KZG_F30_S1(M) M(0)
+#define KZG_F30_S2(M) KZG_F30_S1(M) M(1)
+#define KZG_F30_S3(M) KZG_F30_S2(M) M(2)
+#define KZG_F30_S4(M) KZG_F30_S3(M) M(3)
+#define KZG_F30_S5(M) KZG_F30_S4(M) M(4)
+#define KZG_F30_S6(M) KZG_F30_S5(M) M(5)
+#define KZG_F30_S7(M) KZG_F30_S6(M) M(6)
+#define KZG_F30_S8(M) KZG_F30_S7(M) M(7)
+#define KZG_F30_S9(M) KZG_F30_S8(M) M(8)
+#define KZG_F30_S10(M) KZG_F30_S9(M) M(9)
+#define KZG_F30_S11(M) KZG_F30_S10(M) M(10)
+#define KZG_F30_S12(M) KZG_F30_S11(M) M(11)
+#define KZG_F30_S13(M) KZG_F30_S12(M) M(12)
+#define KZG_F30_L1(M) M(0)
+#define KZG_F30_L2(M) KZG_F30_L1(M), M(1)
+#define KZG_F30_L3(M) KZG_F30_L2(M), M(2)
+#define KZG_F30_L4(M) KZG_F30_L3(M), M(3)
+#define KZG_F30_L5(M) KZG_F30_L4(M), M(4)
+#define KZG_F30_L6(M) KZG_F30_L5(M), M(5)
+#define KZG_F30_L7(M) KZG_F30_L6(M), M(6)
+#define KZG_F30_L8(M) KZG_F30_L7(M), M(7)
+#define KZG_F30_L9(M) KZG_F30_L8(M), M(8)
+#define KZG_F30_L10(M) KZG_F30_L9(M), M(9)
+#define KZG_F30_L11(M) KZG_F30_L10(M), M(10)
+#define KZG_F30_L12(M) KZG_F30_L11(M), M(11)
+#define KZG_F30_L13(M) KZG_F30_L12(M), M(12)
+#define KZG_F30_RUN(n, T) \
+  if constexpr (Cnt == n) \
+    asm(KZG_F30_S##n(KZG_F30_##T) : [c] "+v"(c), [o] "=&s"(carry_out) : KZG_F30_L##n(KZG_F30_##T##_IN));
+#define KZG_F30_RUNS7(T) \
+  KZG_F30_RUN(1, T) KZG_F30_RUN(2, T) KZG_F30_RUN(3, T) KZG_F30_RUN(4, T) KZG_F30_RUN(5, T) KZG_F30_RUN(6, T) \
+  KZG_F30_RUN(7, T)
+#define KZG_F30_RUNS13(T) \
+  KZG_F30_RUNS7(T) KZG_F30_RUN(8, T) KZG_F30_RUN(9, T) KZG_F30_RUN(10, T) KZG_F30_RUN(11, T) KZG_F30_RUN(12, T) \
+  KZG_F30_RUN(13, T)
+// c + x_0 y_0 + ... (Cnt products of two lane values); Cnt = 0: nothing. Zero: c is 0 and enters the first
+// mad as the inline constant, not through a register that a v_mov would have to clear (column 0: one
+// product, f30_mul_addsqr's two)
+template <int Cnt, bool Zero = false>
+KZG_DEV int64_t mad_i64_run(const int32_t (&x)[13], const int32_t (&y)[13], int64_t c) {
+  static_assert(Cnt >= 0 && Cnt <= 13, "a statement takes 30 operands");
+  static_assert(!Zero || Cnt == 1 || Cnt == 2, "a column 0");
+  [[maybe_unused]] uint64_t carry_out;
+  if constexpr (Zero && Cnt == 1) {
+    asm("v_mad_i64_i32 %[c], %[o], %[x0], %[y0], 0" : [c] "=v"(c), [o] "=s"(carry_out) : KZG_F30_VV_IN(0));
+  } else if constexpr (Zero) {
+    asm("v_mad_i64_i32 %[c], %[o], %[x0], %[y0], 0\n\t" KZG_F30_VV(1)
+        : [c] "=&v"(c), [o] "=&s"(carry_out)
+        : KZG_F30_L2(KZG_F30_VV_IN));
+  } else {
+    KZG_F30_RUNS13(VV)
+  }
+  return c;
+}
+// c + m_0 p_0 + ... (Cnt products of a lane value and a wave-uniform constant)
+template <int Cnt>
+KZG_DEV int64_t mad_i64_run_k(const int32_t (&m)[13], const int32_t (&p)[13], int64_t c) {
+  static_assert(Cnt >= 0 && Cnt <= 13, "a statement takes 30 operands");
+  [[maybe_unused]] uint64_t carry_out;
+  KZG_F30_RUNS13(VK)
+  return c;
+}
+// c + x_0 y_0 + m_0 p_0 + x_1 y_1 + m_1 p_1 + ... (Cnt pairs, interleaved)
+template <int Cnt>
+KZG_DEV int64_t mad_i64_pairs(const int32_t (&x)[13], const int32_t (&y)[13], const int32_t (&m)[13],
+                              const int32_t (&p)[13], int64_t c) {
+  static_assert(Cnt >= 0 && Cnt <= 7, "a statement takes 30 operands");
+  [[maybe_unused]] uint64_t carry_out;
+  KZG_F30_RUNS7(PR)
+  return c;
+}
+#undef KZG_F30_RUNS13
+#undef KZG_F30_RUNS7
+#undef KZG_F30_RUN
 // c + a b, c + a k on one accumulator. Chain = true: through the opaque mads above, so that a column is
 // ONE serial chain on the running carry and costs no 64-bit merge at all; left to itself the compiler
 // splits every column into two or three chains and merges them (v_lshl_add_u64, an instruction like
-// any other to a kernel bound by VALU issue). The price is an s_nop between dependent asm mads
-// (~1,360 per ladder doubling), which a second wave on the SIMD hides: the G1 codec, at 2 waves per SIMD
-// on every launch that matters, runs Chain = true; the G2 codec, whose 2^16-point launches put one wave
-// on a SIMD, keeps the compiler's chains (profiles/r10_ab_f30_serial.json).
+// any other to a kernel bound by VALU issue). One mad to a statement pays an s_nop between almost every
+// two mads (~1,360 per ladder doubling: the hazard recogniser's rule for asm statements, above); the
+// f30 products cut their columns into block statements instead (F30_BLOCK below), and both codecs run
+// Chain = true (profiles/r10_ab_f30_serial.json, profiles/r11_ab_f30_blocks.json).
 template <bool Chain>
 KZG_DEV int64_t f30_mac(int32_t a, int32_t b, int64_t c) {
   if constexpr (Chain) return mad_i64_chain(a, b, c);
@@ -590,6 +678,78 @@ KZG_DEV int64_t f30_mac_k(int32_t a, int32_t k, int64_t c) {
   if constexpr (Chain) return mad_i64_chain_k(a, k, c);
   else return c + (int64_t)a * k;
 }
+// How a Chain = true column is cut into asm statements (Block): one mad each; the x y and m p products
+// interleaved, at most 7 pairs to a statement, what is left over as a run; or the x y products as one
+// run and the m p products as another. The integers are the same in every form: only the order of an
+// exact sum changes. KZGPOT_F30_BLOCK picks the codecs' form for an A/B build.
+constexpr int F30_SINGLE = 0, F30_PAIRS = 1, F30_RUNS = 2;
+#ifndef KZGPOT_F30_BLOCK
+#define KZGPOT_F30_BLOCK 2
+#endif
+constexpr int F30_BLOCK = KZGPOT_F30_BLOCK;
+constexpr int F30_NV = 20;  // lane-by-lane products of one column: f30_mul_addsqr's column 12 has 13 + 7
+
+template <int I, int End, class F>
+KZG_DEV void f30_static_for(F&& f) {
+  if constexpr (I < End) {
+    f(std::integral_constant<int, I>{});
+    f30_static_for<I + 1, End>(f);
+  }
+}
+template <int Off, int Cnt, bool Zero = false>
+KZG_DEV int64_t f30_run(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], int64_t acc) {
+  int32_t xs[N30], ys[N30];
+#pragma unroll
+  for (int j = 0; j < Cnt; j++) xs[j] = x[Off + j], ys[j] = y[Off + j];
+  return mad_i64_run<Cnt, Zero>(xs, ys, acc);
+}
+template <int Off, int Cnt>
+KZG_DEV int64_t f30_run_k(const int32_t (&m)[N30], const int32_t (&p)[N30], int64_t acc) {
+  int32_t ms[N30], ps[N30];
+#pragma unroll
+  for (int j = 0; j < Cnt; j++) ms[j] = m[Off + j], ps[j] = p[Off + j];
+  return mad_i64_run_k<Cnt>(ms, ps, acc);
+}
+template <int Off, int Cnt>
+KZG_DEV int64_t f30_pairs(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], const int32_t (&m)[N30],
+                          const int32_t (&p)[N30], int64_t acc) {
+  int32_t xs[N30], ys[N30], ms[N30], ps[N30];
+#pragma unroll
+  for (int j = 0; j < Cnt; j++) xs[j] = x[Off + j], ys[j] = y[Off + j], ms[j] = m[Off + j], ps[j] = p[Off + j];
+  return mad_i64_pairs<Cnt>(xs, ys, ms, ps, acc);
+}
+// acc + x_0 y_0 + ... + x_{NV-1} y_{NV-1} + m_0 p_0 + ... + m_{NK-1} p_{NK-1} in Block's statements; a
+// run too long for one statement is halved. Zero: acc is 0 (column 0, which has no m p product)
+template <int Block, int NV, int NK, bool Zero = false>
+KZG_DEV int64_t f30_col(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], const int32_t (&m)[N30],
+                        const int32_t (&p)[N30], int64_t acc) {
+  static_assert(Block == F30_PAIRS || Block == F30_RUNS, "block form");
+  static_assert(NV >= 0 && NV <= F30_NV && NK >= 0 && NK <= N30, "column");
+  if constexpr (Zero) {
+    static_assert(NK == 0, "column 0");
+    return f30_run<0, NV, true>(x, y, acc);
+  }
+  constexpr int NP = Block == F30_PAIRS ? (NV < NK ? NV : NK) : 0;  // interleaved pairs, then the rest
+  constexpr int P0 = NP > 7 ? (NP + 1) / 2 : NP;
+  acc = f30_pairs<0, P0>(x, y, m, p, acc);
+  acc = f30_pairs<P0, NP - P0>(x, y, m, p, acc);
+  constexpr int RV = NV - NP, V0 = RV > 13 ? (RV + 1) / 2 : RV;
+  acc = f30_run<NP, V0>(x, y, acc);
+  acc = f30_run<NP + V0, RV - V0>(x, y, acc);
+  return f30_run_k<NP, NK - NP>(m, p, acc);
+}
+// the end of column I: m_I and its product (a lower column) or the output digit (an upper one), the carry
+template <int I>
+KZG_DEV int64_t f30_col_end(int64_t acc, int32_t (&m)[N30], f30& r) {
+  if constexpr (I < N30) {
+    m[I] = sext30((uint32_t)acc * PINV30);
+    acc += (int64_t)m[I] * P30[0];
+  } else {
+    r.v[I - N30] = sext30((uint32_t)acc);
+    acc += (int64_t)1 << 29;
+  }
+  return acc >> 30;
+}
 // r = a b 2^-390 mod p for balanced a, b (|digit| <= 2^29, |top digit| <= 2^23: the bound
 // tests/test_fp30.py proves, TOP_IN = 2^23 + 1, and the exponentiation's callers use); r balanced with
 // |value| < p/2 + |a| |b| / R30. The lower columns are made divisible by 2^30 by m_i = balanced
@@ -598,12 +758,26 @@ KZG_DEV int64_t f30_mac_k(int32_t a, int32_t k, int64_t c) {
 // tests/test_fp30.py (the sum started at +2^29, digit (acc & M30) - 2^29, carry acc >> 30), an
 // instruction fewer per column where the bias is no chain's free start addend. Every partial sum is
 // bounded by the sum of absolute values those tests prove, in any order of accumulation.
-template <bool Chain = true>
+template <bool Chain = true, int Block = F30_BLOCK>
 KZG_DEV void f30_mul(f30& r, const f30& a, const f30& b) {
   KZG_FPOP(FpOp::Mul30);
   constexpr int N = N30;
   int32_t m[N];
   int64_t acc = 0;
+  if constexpr (Chain && Block != F30_SINGLE) {
+    f30_static_for<0, 2 * N - 1>([&](auto col) __attribute__((always_inline)) {
+      constexpr int i = decltype(col)::value;
+      constexpr int j0 = i < N ? 0 : i - (N - 1), n = (i < N ? i - 1 : N - 1) - j0 + 1;
+      int32_t x[F30_NV], y[F30_NV], mm[N], pp[N];
+#pragma unroll
+      for (int j = 0; j < n; j++) x[j] = a.v[j0 + j], y[j] = b.v[i - j0 - j], mm[j] = m[j0 + j], pp[j] = P30[i - j0 - j];
+      if constexpr (i < N) x[n] = a.v[i], y[n] = b.v[0];
+      acc = f30_col<Block, n + (i < N), n, i == 0>(x, y, mm, pp, acc);
+      acc = f30_col_end<i>(acc, m, r);
+    });
+    r.v[N - 1] = (int32_t)acc;
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < 2 * N - 1; i++) {
     const int j0 = i < N ? 0 : i - (N - 1);
@@ -629,7 +803,7 @@ KZG_DEV void f30_mul(f30& r, const f30& a, const f30& b) {
 // their a*d products onto the incoming carry in either form (mad_i64_chain: 94.5 against 92.6 G
 // squarings/s, profiles/r03o_mont30_chained.txt); Chain = true chains the lower columns and the m*p
 // products as well.
-template <bool Chain = true>
+template <bool Chain = true, int Block = F30_BLOCK>
 KZG_DEV void f30_sqr(f30& r, const f30& a) {
   KZG_FPOP(FpOp::Sqr30);
   constexpr int N = N30;
@@ -637,6 +811,23 @@ KZG_DEV void f30_sqr(f30& r, const f30& a) {
 #pragma unroll
   for (int j = 0; j < N; j++) d[j] = dbl_i32(a.v[j]);
   int64_t acc = 0;
+  if constexpr (Chain && Block != F30_SINGLE) {
+    f30_static_for<0, 2 * N - 1>([&](auto col) __attribute__((always_inline)) {
+      constexpr int i = decltype(col)::value;
+      constexpr int j0 = i < N ? 0 : i - (N - 1), nk = (i < N ? i - 1 : N - 1) - j0 + 1;
+      constexpr int nc = (i + 1) / 2 - j0, nv = nc + ((i & 1) == 0);  // cross products, then the square
+      int32_t x[F30_NV], y[F30_NV], mm[N], pp[N];
+#pragma unroll
+      for (int j = 0; j < nc; j++) x[j] = a.v[j0 + j], y[j] = d[i - j0 - j];
+      if constexpr ((i & 1) == 0) x[nc] = y[nc] = a.v[i / 2];
+#pragma unroll
+      for (int k = 0; k < nk; k++) mm[k] = m[j0 + k], pp[k] = P30[i - j0 - k];
+      acc = f30_col<Block, nv, nk, i == 0>(x, y, mm, pp, acc);
+      acc = f30_col_end<i>(acc, m, r);
+    });
+    r.v[N - 1] = (int32_t)acc;
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < 2 * N - 1; i++) {
     const int j0 = i < N ? 0 : i - (N - 1);
@@ -695,7 +886,7 @@ KZG_DEV void f30_mul_sum2(f30& r, const f30& a, const f30& b, const f30& c, cons
 }
 // r = (a b + c^2) 2^-390 mod p, the c^2 half as a squaring (cross products once, as c_j (2 c_k)):
 // the 13-digit form of fp_mul_addsqr<1>, the W-form doubling's -W3 = 2E (X3 - D) + B'^2
-template <bool Chain = true>
+template <bool Chain = true, int Block = F30_BLOCK>
 KZG_DEV void f30_mul_addsqr(f30& r, const f30& a, const f30& b, const f30& c) {
   KZG_FPOP(FpOp::Mul30AddSqr);
   constexpr int N = N30;
@@ -703,6 +894,24 @@ KZG_DEV void f30_mul_addsqr(f30& r, const f30& a, const f30& b, const f30& c) {
 #pragma unroll
   for (int j = 0; j < N; j++) c2[j] = dbl_i32(c.v[j]);
   int64_t acc = 0;
+  if constexpr (Chain && Block != F30_SINGLE) {
+    f30_static_for<0, 2 * N - 1>([&](auto col) __attribute__((always_inline)) {
+      constexpr int i = decltype(col)::value;
+      constexpr int j0 = i < N ? 0 : i - (N - 1), n = (i < N ? i - 1 : N - 1) - j0 + 1;
+      constexpr int nc = (i + 1) / 2 - j0, sq = (i & 1) == 0;
+      int32_t x[F30_NV], y[F30_NV], mm[N], pp[N];
+#pragma unroll
+      for (int j = 0; j < n; j++) x[j] = a.v[j0 + j], y[j] = b.v[i - j0 - j], mm[j] = m[j0 + j], pp[j] = P30[i - j0 - j];
+#pragma unroll
+      for (int j = 0; j < nc; j++) x[n + j] = c.v[j0 + j], y[n + j] = c2[i - j0 - j];
+      if constexpr (sq) x[n + nc] = y[n + nc] = c.v[i / 2];
+      if constexpr (i < N) x[n + nc + sq] = a.v[i], y[n + nc + sq] = b.v[0];
+      acc = f30_col<Block, n + nc + sq + (i < N), n, i == 0>(x, y, mm, pp, acc);
+      acc = f30_col_end<i>(acc, m, r);
+    });
+    r.v[N - 1] = (int32_t)acc;
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < 2 * N - 1; i++) {
     const int j0 = i < N ? 0 : i - (N - 1);

@@ -155,7 +155,11 @@ __device__ __forceinline__ void sqr30c(int32_t (&r)[N30], const int32_t (&a)[N30
 using kzgpot::fp;
 constexpr int N28 = kzgpot::NL;
 
-// V: 0 fp_mul (14 x 28), 1 fp_sqr (14 x 28), 2 mul30, 3 sqr30. CH independent chains per lane.
+// V: 0 fp_mul (14 x 28), 1 fp_sqr (14 x 28), 2 mul30, 3 sqr30, 4 / 5 the same with the upper columns
+// chained; 6 ... 11 the codec's own serial-chain forms, kzgpot::f30_mul<true, B> (even V) and
+// f30_sqr<true, B> (odd V) with B = (V - 6) / 2: one mad to an asm statement, a b / m p pairs to a
+// statement, whole runs to a statement (fp381.hpp F30_SINGLE, F30_PAIRS, F30_RUNS).
+// CH independent chains per lane.
 template <int V, int CH>
 __global__ void __launch_bounds__(256) kbench(uint32_t* out, const uint32_t* in, int iters, int lds_pad) {
   extern __shared__ uint32_t pad[];
@@ -181,6 +185,29 @@ __global__ void __launch_bounds__(256) kbench(uint32_t* out, const uint32_t* in,
     for (int c = 0; c < CH; c++)
 #pragma unroll
       for (int j = 0; j < N28; j++) s += x[c].v[j] * (j + 1);
+  } else if constexpr (V >= 6) {
+    constexpr int B = (V - 6) / 2;
+    kzgpot::f30 x[CH], y;
+#pragma unroll
+    for (int j = 0; j < N30; j++) {
+      y.v[j] = j == 12 ? (int32_t)(in[(tid * 7 + j) & 1023] & 0xfffffu) : sext30(in[(tid * 7 + j) & 1023]);
+#pragma unroll
+      for (int c = 0; c < CH; c++) {
+        const uint32_t w = in[(tid * 13 + j + 13 * c + 100) & 1023];
+        x[c].v[j] = j == 12 ? (int32_t)(w & 0xfffffu) : sext30(w);
+      }
+    }
+    for (int it = 0; it < iters; it++) {
+#pragma unroll
+      for (int c = 0; c < CH; c++) {
+        if (V & 1) kzgpot::f30_sqr<true, B>(x[c], x[c]);
+        else kzgpot::f30_mul<true, B>(x[c], x[c], y);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CH; c++)
+#pragma unroll
+      for (int j = 0; j < N30; j++) s += (uint32_t)x[c].v[j] * (j + 1);
   } else {
     int32_t x[CH][N30], y[N30];
 #pragma unroll
@@ -210,7 +237,17 @@ __global__ void __launch_bounds__(256) kbench(uint32_t* out, const uint32_t* in,
   out[tid] = s;
 }
 
-// correctness dump: 256 lanes, a (13 limbs), b, a*b, a^2
+// correctness dump: 256 lanes, a (13 limbs), b, a*b, a^2; then the chained variants' a*b, a^2; then
+// those of f30_mul / f30_sqr<true, B> for B = 0, 1, 2
+template <int B>
+__device__ void check_blocks(int32_t* out, const int32_t (&a)[N30], const int32_t (&b)[N30]) {
+  kzgpot::f30 x, y, r;
+  for (int j = 0; j < N30; j++) x.v[j] = a[j], y.v[j] = b[j];
+  kzgpot::f30_mul<true, B>(r, x, y);
+  for (int j = 0; j < N30; j++) out[j] = r.v[j];
+  kzgpot::f30_sqr<true, B>(r, x);
+  for (int j = 0; j < N30; j++) out[13 + j] = r.v[j];
+}
 __global__ void kcheck30(int32_t* out, const int32_t* in) {
   const int t = threadIdx.x;
   int32_t a[N30], b[N30], r[N30];
@@ -223,6 +260,9 @@ __global__ void kcheck30(int32_t* out, const int32_t* in) {
   mul30c(r2, a, b);
   sqr30c(r, a);
   for (int j = 0; j < N30; j++) out[256 * 52 + t * 26 + j] = r2[j], out[256 * 52 + t * 26 + 13 + j] = r[j];
+  check_blocks<0>(out + 256 * 78 + t * 26, a, b);
+  check_blocks<1>(out + 256 * 104 + t * 26, a, b);
+  check_blocks<2>(out + 256 * 130 + t * 26, a, b);
 }
 
 int main(int argc, char** argv) {
@@ -234,7 +274,7 @@ int main(int argc, char** argv) {
   uint64_t s = 0x9e3779b97f4a7c15ULL;
   for (int i = 0; i < 4096; i++) { s = s * 6364136223846793005ULL + 1; hin[i] = (uint32_t)(s >> 32); }
   {  // check inputs: random balanced limbs, plus extreme lanes (every limb at -2^29 or 2^29 - 1)
-    static int32_t cin[256 * 26], cout[256 * 52 + 256 * 26];
+    static int32_t cin[256 * 26], cout[256 * 156];
     for (int t = 0; t < 256; t++)
       for (int j = 0; j < 26; j++) {
         const int k = j % 13;
@@ -260,12 +300,15 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1;
   CHECK(hipEventCreate(&e0));
   CHECK(hipEventCreate(&e1));
-  const char* nm[6] = {"fp_mul 14x28", "fp_sqr 14x28", "mul30 13x30s", "sqr30 13x30s", "mul30 chained", "sqr30 chained"};
+  const char* nm[12] = {"fp_mul 14x28", "fp_sqr 14x28", "mul30 13x30s", "sqr30 13x30s", "mul30 chained", "sqr30 chained",
+                        "f30_mul single", "f30_sqr single", "f30_mul pairs", "f30_sqr pairs", "f30_mul runs", "f30_sqr runs"};
   for (int pass = 0; pass < 2; pass++)
-    for (int v = 0; v < 6; v++)
+    for (int v = 0; v < 12; v++)
       for (int ch = 1; ch <= 2; ch++)
-        for (int occ = 2; occ <= 4; occ += 2) {
-          const size_t lds = (160 * 1024) / occ - 1024;
+        // the serial-chain forms at one and two waves per SIMD (the codec's occupancy), the others as before
+        for (int occ = v < 6 ? 2 : 1; occ <= (v < 6 ? 4 : 2); occ *= 2) {
+          // one block (4 waves) to a CU at occ = 1: more than half of the CU's 160 KiB
+          const size_t lds = occ == 1 ? 96 * 1024 : (160 * 1024) / occ - 1024;
           const int iters = 64;
           float ms = 0;
           CHECK(hipEventRecord(e0));
@@ -277,6 +320,12 @@ int main(int argc, char** argv) {
             if (v == 3) L(3, 1);
             if (v == 4) L(4, 1);
             if (v == 5) L(5, 1);
+            if (v == 6) L(6, 1);
+            if (v == 7) L(7, 1);
+            if (v == 8) L(8, 1);
+            if (v == 9) L(9, 1);
+            if (v == 10) L(10, 1);
+            if (v == 11) L(11, 1);
           } else {
             if (v == 0) L(0, 2);
             if (v == 1) L(1, 2);
@@ -284,6 +333,12 @@ int main(int argc, char** argv) {
             if (v == 3) L(3, 2);
             if (v == 4) L(4, 2);
             if (v == 5) L(5, 2);
+            if (v == 6) L(6, 2);
+            if (v == 7) L(7, 2);
+            if (v == 8) L(8, 2);
+            if (v == 9) L(9, 2);
+            if (v == 10) L(10, 2);
+            if (v == 11) L(11, 2);
           }
 #undef L
           CHECK(hipEventRecord(e1));
