@@ -64,7 +64,7 @@ KZG_DEV bool fp2_sqrt(fp2& y, const fp2& a) {
   // <true>: the serial chains of the radix-2^30 core. Cut into block statements they no longer pay a pad
   // per mad, which a 2^16-point G2 launch (one wave on a SIMD) could not hide: that launch is 1.7 %
   // faster than with the compiler's chains, G2 phase 1 at 2^20 3.3 % (profiles/r11_ab_f30_blocks.json)
-  fp_pow_pm3d4<true>(t0, nrm);
+  fp_pow_pm3d4(t0, nrm);
   fp_mul(gam, t0, nrm);
   fp_sqr(t0, gam);
   const bool square = fp_eq(t0, nrm);  // gam^2 == N
@@ -72,7 +72,7 @@ KZG_DEV bool fp2_sqrt(fp2& y, const fp2& a) {
   fp_norm(d, d);
   fp_half(d, d);  // (a0 + gam) / 2
   fp_select(d, fp_is_zero(d), a.c0, d);
-  fp_pow_pm3d4<true>(t0, d);  // t
+  fp_pow_pm3d4(t0, d);  // t
   fp_mul(s, t0, d);
   fp_half(h, a.c1);
   fp_mul(h, h, t0);  // a1 t / 2

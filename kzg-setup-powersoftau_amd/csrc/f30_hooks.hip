@@ -21,9 +21,9 @@ __device__ __forceinline__ void f30_load(f30& x, const int32_t* p, long i) {
 
 constexpr int arity(int op) {
   return op == KZGPOT_F30_MUL_SUM2 ? 4
-         : op == KZGPOT_F30_MUL_ADDSQR || op == KZGPOT_F30_MUL_ADDSQR_C ? 3
-         : op == KZGPOT_F30_MUL || op == KZGPOT_F30_MUL_C ? 2
-                                                           : 1;
+         : op == KZGPOT_F30_MUL_ADDSQR ? 3
+         : op == KZGPOT_F30_MUL ? 2
+                                : 1;
 }
 
 template <int OP>
@@ -37,13 +37,9 @@ __global__ void __launch_bounds__(kBlock) k_f30_op(long n, const int32_t* __rest
   if (arity(OP) >= 2) f30_load(y, b, i);
   if (arity(OP) >= 3) f30_load(z, c, i);
   if (arity(OP) >= 4) f30_load(w, d, i);
-  // the serial-chain forms (the codecs') and, _C, the compiler's chains
-  if (OP == KZGPOT_F30_MUL) f30_mul<true>(o, x, y);
-  if (OP == KZGPOT_F30_SQR) f30_sqr<true>(o, x);
-  if (OP == KZGPOT_F30_MUL_ADDSQR) f30_mul_addsqr<true>(o, x, y, z);
-  if (OP == KZGPOT_F30_MUL_C) f30_mul<false>(o, x, y);
-  if (OP == KZGPOT_F30_SQR_C) f30_sqr<false>(o, x);
-  if (OP == KZGPOT_F30_MUL_ADDSQR_C) f30_mul_addsqr<false>(o, x, y, z);
+  if (OP == KZGPOT_F30_MUL) f30_mul(o, x, y);
+  if (OP == KZGPOT_F30_SQR) f30_sqr(o, x);
+  if (OP == KZGPOT_F30_MUL_ADDSQR) f30_mul_addsqr(o, x, y, z);
   if (OP == KZGPOT_F30_MUL_SUM2) f30_mul_sum2(o, x, y, z, w);
   if (OP == KZGPOT_F30_DBL) f30_dbl(o, x);
   if (OP == KZGPOT_F30_MUL3) f30_mul3(o, x);
@@ -94,9 +90,6 @@ extern "C" int kzgpot_test_f30_op(int op, long n, const int32_t* a, const int32_
     case KZGPOT_F30_NORM1: return run_op<KZGPOT_F30_NORM1>(n, a, b, c, d, r);
     case KZGPOT_F30_NORM2: return run_op<KZGPOT_F30_NORM2>(n, a, b, c, d, r);
     case KZGPOT_F30_NORM3: return run_op<KZGPOT_F30_NORM3>(n, a, b, c, d, r);
-    case KZGPOT_F30_MUL_C: return run_op<KZGPOT_F30_MUL_C>(n, a, b, c, d, r);
-    case KZGPOT_F30_SQR_C: return run_op<KZGPOT_F30_SQR_C>(n, a, b, c, d, r);
-    case KZGPOT_F30_MUL_ADDSQR_C: return run_op<KZGPOT_F30_MUL_ADDSQR_C>(n, a, b, c, d, r);
     default: return KZGPOT_E_INVALID_ARG;
   }
 }

@@ -558,34 +558,22 @@ struct f30 {
 };
 KZG_DEV int32_t sext30(uint32_t x) { return __builtin_amdgcn_sbfe((int32_t)x, 0, 30); }
 
-// a b + c as one opaque v_mad_i64_i32 (its carry-out goes to a scratch SGPR pair): a chain of these
-// cannot be re-associated by the compiler. mad_i64_chain_k: b a wave-uniform constant in an SGPR (a
-// digit of p).
-KZG_DEV int64_t mad_i64_chain(int32_t a, int32_t b, int64_t c) {
-  int64_t r;
-  uint64_t carry_out;
-  asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry_out) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-KZG_DEV int64_t mad_i64_chain_k(int32_t a, int32_t k, int64_t c) {
-  int64_t r;
-  uint64_t carry_out;
-  asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry_out) : "v"(a), "s"(k), "v"(c));
-  return r;
-}
-// Blocks: a run of dependent mads on ONE accumulator as ONE asm statement. The compiler's hazard
-// recogniser pads between two asm statements that define the same register (here the carry-out pair: one
-// s_nop 0 per statement) and pads nothing inside a statement, and back-to-back dependent
-// v_mad_i64_i32 need no wait state. The accumulator is tied in and out; the carry-out pair is
-// EARLY-CLOBBER, since the first mad writes it before the later ones have read their digit of p from
-// an SGPR. gfx9 VOP3 takes no literal and one SGPR source, so a digit of p is an "s" operand, one per
-// mad; a statement takes 30 operands, so a run holds at most 13 products (28) or 7 a b / m p pairs (30).
+// A column of a product is ONE serial chain of v_mad_i64_i32 on the running carry, written as asm so
+// that the compiler cannot re-associate it: left to itself it splits every column into two or three
+// chains and merges them (v_lshl_add_u64, an instruction like any other to a kernel bound by VALU
+// issue). A run of dependent mads on the accumulator is ONE asm statement: the compiler's hazard
+// recogniser pads between two asm statements that define the same register (here the carry-out pair,
+// a scratch SGPR pair: one s_nop 0 per statement) and pads nothing inside a statement, and
+// back-to-back dependent v_mad_i64_i32 need no wait state. The accumulator is tied in and out; the
+// carry-out pair is EARLY-CLOBBER, since the first mad writes it before the later ones have read their
+// digit of p from an SGPR. gfx9 VOP3 takes no literal and one SGPR source, so a digit of p is an "s"
+// operand, one per mad; a statement takes 30 operands, so a run holds at most 13 products (28).
+// Measured against the compiler's own chains and against other cuts of a column into statements:
+// DESIGN §4, profiles/r10_ab_f30_serial.json, profiles/r11_ab_f30_blocks.json.
 #define KZG_F30_VV(k) "v_mad_i64_i32 %[c], %[o], %[x" #k "], %[y" #k "], %[c]\n\t"
 #define KZG_F30_VK(k) "v_mad_i64_i32 %[c], %[o], %[m" #k "], %[p" #k "], %[c]\n\t"
-#define KZG_F30_PR(k) KZG_F30_VV(k) KZG_F30_VK(k)
 #define KZG_F30_VV_IN(k) [x##k] "v"(x[k]), [y##k] "v"(y[k])
 #define KZG_F30_VK_IN(k) [m##k] "v"(m[k]), [p##k] "s"(p[k])
-#define KZG_F30_PR_IN(k) KZG_F30_VV_IN(k), KZG_F30_VK_IN(k)
 // KZG_F30_Sn(M): M(0) ... M(n-1) side by side (the string); KZG_F30_Ln(M): comma-separated (the operands)
 #define KZG_F30_S1(M) M(0)
 #define KZG_F30_S2(M) KZG_F30_S1(M) M(1)
@@ -616,11 +604,9 @@ KZG_DEV int64_t mad_i64_chain_k(int32_t a, int32_t k, int64_t c) {
 #define KZG_F30_RUN(n, T) \
   if constexpr (Cnt == n) \
     asm(KZG_F30_S##n(KZG_F30_##T) : [c] "+v"(c), [o] "=&s"(carry_out) : KZG_F30_L##n(KZG_F30_##T##_IN));
-#define KZG_F30_RUNS7(T) \
-  KZG_F30_RUN(1, T) KZG_F30_RUN(2, T) KZG_F30_RUN(3, T) KZG_F30_RUN(4, T) KZG_F30_RUN(5, T) KZG_F30_RUN(6, T) \
-  KZG_F30_RUN(7, T)
 #define KZG_F30_RUNS13(T) \
-  KZG_F30_RUNS7(T) KZG_F30_RUN(8, T) KZG_F30_RUN(9, T) KZG_F30_RUN(10, T) KZG_F30_RUN(11, T) KZG_F30_RUN(12, T) \
+  KZG_F30_RUN(1, T) KZG_F30_RUN(2, T) KZG_F30_RUN(3, T) KZG_F30_RUN(4, T) KZG_F30_RUN(5, T) KZG_F30_RUN(6, T) \
+  KZG_F30_RUN(7, T) KZG_F30_RUN(8, T) KZG_F30_RUN(9, T) KZG_F30_RUN(10, T) KZG_F30_RUN(11, T) KZG_F30_RUN(12, T) \
   KZG_F30_RUN(13, T)
 // c + x_0 y_0 + ... (Cnt products of two lane values); Cnt = 0: nothing. Zero: c is 0 and enters the first
 // mad as the inline constant, not through a register that a v_mov would have to clear (column 0: one
@@ -649,44 +635,8 @@ KZG_DEV int64_t mad_i64_run_k(const int32_t (&m)[13], const int32_t (&p)[13], in
   KZG_F30_RUNS13(VK)
   return c;
 }
-// c + x_0 y_0 + m_0 p_0 + x_1 y_1 + m_1 p_1 + ... (Cnt pairs, interleaved)
-template <int Cnt>
-KZG_DEV int64_t mad_i64_pairs(const int32_t (&x)[13], const int32_t (&y)[13], const int32_t (&m)[13],
-                              const int32_t (&p)[13], int64_t c) {
-  static_assert(Cnt >= 0 && Cnt <= 7, "a statement takes 30 operands");
-  [[maybe_unused]] uint64_t carry_out;
-  KZG_F30_RUNS7(PR)
-  return c;
-}
 #undef KZG_F30_RUNS13
-#undef KZG_F30_RUNS7
 #undef KZG_F30_RUN
-// c + a b, c + a k on one accumulator. Chain = true: through the opaque mads above, so that a column is
-// ONE serial chain on the running carry and costs no 64-bit merge at all; left to itself the compiler
-// splits every column into two or three chains and merges them (v_lshl_add_u64, an instruction like
-// any other to a kernel bound by VALU issue). One mad to a statement pays an s_nop between almost every
-// two mads (~1,360 per ladder doubling: the hazard recogniser's rule for asm statements, above); the
-// f30 products cut their columns into block statements instead (F30_BLOCK below), and both codecs run
-// Chain = true (profiles/r10_ab_f30_serial.json, profiles/r11_ab_f30_blocks.json).
-template <bool Chain>
-KZG_DEV int64_t f30_mac(int32_t a, int32_t b, int64_t c) {
-  if constexpr (Chain) return mad_i64_chain(a, b, c);
-  else return c + (int64_t)a * b;
-}
-template <bool Chain>
-KZG_DEV int64_t f30_mac_k(int32_t a, int32_t k, int64_t c) {
-  if constexpr (Chain) return mad_i64_chain_k(a, k, c);
-  else return c + (int64_t)a * k;
-}
-// How a Chain = true column is cut into asm statements (Block): one mad each; the x y and m p products
-// interleaved, at most 7 pairs to a statement, what is left over as a run; or the x y products as one
-// run and the m p products as another. The integers are the same in every form: only the order of an
-// exact sum changes. KZGPOT_F30_BLOCK picks the codecs' form for an A/B build.
-constexpr int F30_SINGLE = 0, F30_PAIRS = 1, F30_RUNS = 2;
-#ifndef KZGPOT_F30_BLOCK
-#define KZGPOT_F30_BLOCK 2
-#endif
-constexpr int F30_BLOCK = KZGPOT_F30_BLOCK;
 constexpr int F30_NV = 20;  // lane-by-lane products of one column: f30_mul_addsqr's column 12 has 13 + 7
 
 template <int I, int End, class F>
@@ -696,6 +646,7 @@ KZG_DEV void f30_static_for(F&& f) {
     f30_static_for<I + 1, End>(f);
   }
 }
+// the lane-by-lane products Off ... Off + Cnt - 1 of a column as one statement
 template <int Off, int Cnt, bool Zero = false>
 KZG_DEV int64_t f30_run(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], int64_t acc) {
   int32_t xs[N30], ys[N30];
@@ -703,40 +654,21 @@ KZG_DEV int64_t f30_run(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], 
   for (int j = 0; j < Cnt; j++) xs[j] = x[Off + j], ys[j] = y[Off + j];
   return mad_i64_run<Cnt, Zero>(xs, ys, acc);
 }
-template <int Off, int Cnt>
-KZG_DEV int64_t f30_run_k(const int32_t (&m)[N30], const int32_t (&p)[N30], int64_t acc) {
-  int32_t ms[N30], ps[N30];
-#pragma unroll
-  for (int j = 0; j < Cnt; j++) ms[j] = m[Off + j], ps[j] = p[Off + j];
-  return mad_i64_run_k<Cnt>(ms, ps, acc);
-}
-template <int Off, int Cnt>
-KZG_DEV int64_t f30_pairs(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], const int32_t (&m)[N30],
-                          const int32_t (&p)[N30], int64_t acc) {
-  int32_t xs[N30], ys[N30], ms[N30], ps[N30];
-#pragma unroll
-  for (int j = 0; j < Cnt; j++) xs[j] = x[Off + j], ys[j] = y[Off + j], ms[j] = m[Off + j], ps[j] = p[Off + j];
-  return mad_i64_pairs<Cnt>(xs, ys, ms, ps, acc);
-}
-// acc + x_0 y_0 + ... + x_{NV-1} y_{NV-1} + m_0 p_0 + ... + m_{NK-1} p_{NK-1} in Block's statements; a
-// run too long for one statement is halved. Zero: acc is 0 (column 0, which has no m p product)
-template <int Block, int NV, int NK, bool Zero = false>
+// acc + x_0 y_0 + ... + x_{NV-1} y_{NV-1} + m_0 p_0 + ... + m_{NK-1} p_{NK-1}: the x y products as one
+// run (halved when too long for one statement), then the m p products as another. Zero: acc is 0
+// (column 0, which has no m p product)
+template <int NV, int NK, bool Zero = false>
 KZG_DEV int64_t f30_col(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], const int32_t (&m)[N30],
                         const int32_t (&p)[N30], int64_t acc) {
-  static_assert(Block == F30_PAIRS || Block == F30_RUNS, "block form");
   static_assert(NV >= 0 && NV <= F30_NV && NK >= 0 && NK <= N30, "column");
   if constexpr (Zero) {
     static_assert(NK == 0, "column 0");
     return f30_run<0, NV, true>(x, y, acc);
   }
-  constexpr int NP = Block == F30_PAIRS ? (NV < NK ? NV : NK) : 0;  // interleaved pairs, then the rest
-  constexpr int P0 = NP > 7 ? (NP + 1) / 2 : NP;
-  acc = f30_pairs<0, P0>(x, y, m, p, acc);
-  acc = f30_pairs<P0, NP - P0>(x, y, m, p, acc);
-  constexpr int RV = NV - NP, V0 = RV > 13 ? (RV + 1) / 2 : RV;
-  acc = f30_run<NP, V0>(x, y, acc);
-  acc = f30_run<NP + V0, RV - V0>(x, y, acc);
-  return f30_run_k<NP, NK - NP>(m, p, acc);
+  constexpr int V0 = NV > 13 ? (NV + 1) / 2 : NV;
+  acc = f30_run<0, V0>(x, y, acc);
+  acc = f30_run<V0, NV - V0>(x, y, acc);
+  return mad_i64_run_k<NK>(m, p, acc);
 }
 // the end of column I: m_I and its product (a lower column) or the output digit (an upper one), the carry
 template <int I>
@@ -750,6 +682,19 @@ KZG_DEV int64_t f30_col_end(int64_t acc, int32_t (&m)[N30], f30& r) {
   }
   return acc >> 30;
 }
+// Column I of a product whose NV lane-by-lane products the caller has put into x, y: the m_j p_{I-j}
+// products of the reduction join them, then the column's end. After column 2 N30 - 2 the carry is the
+// top digit.
+template <int I, int NV>
+KZG_DEV int64_t f30_column(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], int64_t acc, int32_t (&m)[N30],
+                           f30& r) {
+  constexpr int j0 = I < N30 ? 0 : I - (N30 - 1), nk = (I < N30 ? I - 1 : N30 - 1) - j0 + 1;
+  int32_t mm[N30], pp[N30];
+#pragma unroll
+  for (int k = 0; k < nk; k++) mm[k] = m[j0 + k], pp[k] = P30[I - j0 - k];
+  acc = f30_col<NV, nk, I == 0>(x, y, mm, pp, acc);
+  return f30_col_end<I>(acc, m, r);
+}
 // r = a b 2^-390 mod p for balanced a, b (|digit| <= 2^29, |top digit| <= 2^23: the bound
 // tests/test_fp30.py proves, TOP_IN = 2^23 + 1, and the exponentiation's callers use); r balanced with
 // |value| < p/2 + |a| |b| / R30. The lower columns are made divisible by 2^30 by m_i = balanced
@@ -758,52 +703,23 @@ KZG_DEV int64_t f30_col_end(int64_t acc, int32_t (&m)[N30], f30& r) {
 // tests/test_fp30.py (the sum started at +2^29, digit (acc & M30) - 2^29, carry acc >> 30), an
 // instruction fewer per column where the bias is no chain's free start addend. Every partial sum is
 // bounded by the sum of absolute values those tests prove, in any order of accumulation.
-template <bool Chain = true, int Block = F30_BLOCK>
 KZG_DEV void f30_mul(f30& r, const f30& a, const f30& b) {
   KZG_FPOP(FpOp::Mul30);
   constexpr int N = N30;
   int32_t m[N];
   int64_t acc = 0;
-  if constexpr (Chain && Block != F30_SINGLE) {
-    f30_static_for<0, 2 * N - 1>([&](auto col) __attribute__((always_inline)) {
-      constexpr int i = decltype(col)::value;
-      constexpr int j0 = i < N ? 0 : i - (N - 1), n = (i < N ? i - 1 : N - 1) - j0 + 1;
-      int32_t x[F30_NV], y[F30_NV], mm[N], pp[N];
+  f30_static_for<0, 2 * N - 1>([&](auto col) __attribute__((always_inline)) {
+    constexpr int i = decltype(col)::value;
+    constexpr int j0 = i < N ? 0 : i - (N - 1), n = (i < N ? i - 1 : N - 1) - j0 + 1;
+    int32_t x[F30_NV], y[F30_NV];
 #pragma unroll
-      for (int j = 0; j < n; j++) x[j] = a.v[j0 + j], y[j] = b.v[i - j0 - j], mm[j] = m[j0 + j], pp[j] = P30[i - j0 - j];
-      if constexpr (i < N) x[n] = a.v[i], y[n] = b.v[0];
-      acc = f30_col<Block, n + (i < N), n, i == 0>(x, y, mm, pp, acc);
-      acc = f30_col_end<i>(acc, m, r);
-    });
-    r.v[N - 1] = (int32_t)acc;
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 2 * N - 1; i++) {
-    const int j0 = i < N ? 0 : i - (N - 1);
-    const int j1 = i < N ? i - 1 : N - 1;
-#pragma unroll
-    for (int j = j0; j <= j1; j++) {
-      acc = f30_mac<Chain>(a.v[j], b.v[i - j], acc);
-      acc = f30_mac_k<Chain>(m[j], P30[i - j], acc);
-    }
-    if (i < N) {
-      acc = f30_mac<Chain>(a.v[i], b.v[0], acc);
-      m[i] = sext30((uint32_t)acc * PINV30);
-      acc += (int64_t)m[i] * P30[0];
-    } else {
-      r.v[i - N] = sext30((uint32_t)acc);
-      acc += (int64_t)1 << 29;
-    }
-    acc >>= 30;
-  }
+    for (int j = 0; j < n; j++) x[j] = a.v[j0 + j], y[j] = b.v[i - j0 - j];
+    if constexpr (i < N) x[n] = a.v[i], y[n] = b.v[0];
+    acc = f30_column<i, n + (i < N)>(x, y, acc, m, r);
+  });
   r.v[N - 1] = (int32_t)acc;
 }
-// r = a^2 2^-390: cross products once as a_j (2 a_k), the same reduction. The upper columns chain
-// their a*d products onto the incoming carry in either form (mad_i64_chain: 94.5 against 92.6 G
-// squarings/s, profiles/r03o_mont30_chained.txt); Chain = true chains the lower columns and the m*p
-// products as well.
-template <bool Chain = true, int Block = F30_BLOCK>
+// r = a^2 2^-390: cross products once as a_j (2 a_k), the same reduction
 KZG_DEV void f30_sqr(f30& r, const f30& a) {
   KZG_FPOP(FpOp::Sqr30);
   constexpr int N = N30;
@@ -811,43 +727,16 @@ KZG_DEV void f30_sqr(f30& r, const f30& a) {
 #pragma unroll
   for (int j = 0; j < N; j++) d[j] = dbl_i32(a.v[j]);
   int64_t acc = 0;
-  if constexpr (Chain && Block != F30_SINGLE) {
-    f30_static_for<0, 2 * N - 1>([&](auto col) __attribute__((always_inline)) {
-      constexpr int i = decltype(col)::value;
-      constexpr int j0 = i < N ? 0 : i - (N - 1), nk = (i < N ? i - 1 : N - 1) - j0 + 1;
-      constexpr int nc = (i + 1) / 2 - j0, nv = nc + ((i & 1) == 0);  // cross products, then the square
-      int32_t x[F30_NV], y[F30_NV], mm[N], pp[N];
+  f30_static_for<0, 2 * N - 1>([&](auto col) __attribute__((always_inline)) {
+    constexpr int i = decltype(col)::value;
+    constexpr int j0 = i < N ? 0 : i - (N - 1);
+    constexpr int nc = (i + 1) / 2 - j0, sq = (i & 1) == 0;  // cross products, then the square
+    int32_t x[F30_NV], y[F30_NV];
 #pragma unroll
-      for (int j = 0; j < nc; j++) x[j] = a.v[j0 + j], y[j] = d[i - j0 - j];
-      if constexpr ((i & 1) == 0) x[nc] = y[nc] = a.v[i / 2];
-#pragma unroll
-      for (int k = 0; k < nk; k++) mm[k] = m[j0 + k], pp[k] = P30[i - j0 - k];
-      acc = f30_col<Block, nv, nk, i == 0>(x, y, mm, pp, acc);
-      acc = f30_col_end<i>(acc, m, r);
-    });
-    r.v[N - 1] = (int32_t)acc;
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 2 * N - 1; i++) {
-    const int j0 = i < N ? 0 : i - (N - 1);
-    const int k1 = i < N ? i - 1 : N - 1;
-#pragma unroll
-    for (int j = j0; 2 * j < i; j++)
-      acc = i >= N ? mad_i64_chain(a.v[j], d[i - j], acc) : f30_mac<Chain>(a.v[j], d[i - j], acc);
-    if ((i & 1) == 0)
-      acc = i >= N ? mad_i64_chain(a.v[i / 2], a.v[i / 2], acc) : f30_mac<Chain>(a.v[i / 2], a.v[i / 2], acc);
-#pragma unroll
-    for (int k = j0; k <= k1; k++) acc = f30_mac_k<Chain>(m[k], P30[i - k], acc);
-    if (i < N) {
-      m[i] = sext30((uint32_t)acc * PINV30);
-      acc += (int64_t)m[i] * P30[0];
-    } else {
-      r.v[i - N] = sext30((uint32_t)acc);
-      acc += (int64_t)1 << 29;
-    }
-    acc >>= 30;
-  }
+    for (int j = 0; j < nc; j++) x[j] = a.v[j0 + j], y[j] = d[i - j0 - j];
+    if constexpr (sq) x[nc] = y[nc] = a.v[i / 2];
+    acc = f30_column<i, nc + sq>(x, y, acc, m, r);
+  });
   r.v[N - 1] = (int32_t)acc;
 }
 // ---- the forms the G1 subgroup ladders need (curve.hpp, jac<f30>). Operand discipline, proven by
@@ -886,7 +775,6 @@ KZG_DEV void f30_mul_sum2(f30& r, const f30& a, const f30& b, const f30& c, cons
 }
 // r = (a b + c^2) 2^-390 mod p, the c^2 half as a squaring (cross products once, as c_j (2 c_k)):
 // the 13-digit form of fp_mul_addsqr<1>, the W-form doubling's -W3 = 2E (X3 - D) + B'^2
-template <bool Chain = true, int Block = F30_BLOCK>
 KZG_DEV void f30_mul_addsqr(f30& r, const f30& a, const f30& b, const f30& c) {
   KZG_FPOP(FpOp::Mul30AddSqr);
   constexpr int N = N30;
@@ -894,46 +782,19 @@ KZG_DEV void f30_mul_addsqr(f30& r, const f30& a, const f30& b, const f30& c) {
 #pragma unroll
   for (int j = 0; j < N; j++) c2[j] = dbl_i32(c.v[j]);
   int64_t acc = 0;
-  if constexpr (Chain && Block != F30_SINGLE) {
-    f30_static_for<0, 2 * N - 1>([&](auto col) __attribute__((always_inline)) {
-      constexpr int i = decltype(col)::value;
-      constexpr int j0 = i < N ? 0 : i - (N - 1), n = (i < N ? i - 1 : N - 1) - j0 + 1;
-      constexpr int nc = (i + 1) / 2 - j0, sq = (i & 1) == 0;
-      int32_t x[F30_NV], y[F30_NV], mm[N], pp[N];
+  f30_static_for<0, 2 * N - 1>([&](auto col) __attribute__((always_inline)) {
+    constexpr int i = decltype(col)::value;
+    constexpr int j0 = i < N ? 0 : i - (N - 1), n = (i < N ? i - 1 : N - 1) - j0 + 1;
+    constexpr int nc = (i + 1) / 2 - j0, sq = (i & 1) == 0;
+    int32_t x[F30_NV], y[F30_NV];
 #pragma unroll
-      for (int j = 0; j < n; j++) x[j] = a.v[j0 + j], y[j] = b.v[i - j0 - j], mm[j] = m[j0 + j], pp[j] = P30[i - j0 - j];
+    for (int j = 0; j < n; j++) x[j] = a.v[j0 + j], y[j] = b.v[i - j0 - j];
 #pragma unroll
-      for (int j = 0; j < nc; j++) x[n + j] = c.v[j0 + j], y[n + j] = c2[i - j0 - j];
-      if constexpr (sq) x[n + nc] = y[n + nc] = c.v[i / 2];
-      if constexpr (i < N) x[n + nc + sq] = a.v[i], y[n + nc + sq] = b.v[0];
-      acc = f30_col<Block, n + nc + sq + (i < N), n, i == 0>(x, y, mm, pp, acc);
-      acc = f30_col_end<i>(acc, m, r);
-    });
-    r.v[N - 1] = (int32_t)acc;
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 2 * N - 1; i++) {
-    const int j0 = i < N ? 0 : i - (N - 1);
-    const int j1 = i < N ? i - 1 : N - 1;
-#pragma unroll
-    for (int j = j0; j <= j1; j++) {
-      acc = f30_mac<Chain>(a.v[j], b.v[i - j], acc);
-      acc = f30_mac_k<Chain>(m[j], P30[i - j], acc);
-    }
-#pragma unroll
-    for (int j = j0; 2 * j < i; j++) acc = f30_mac<Chain>(c.v[j], c2[i - j], acc);
-    if ((i & 1) == 0) acc = f30_mac<Chain>(c.v[i / 2], c.v[i / 2], acc);
-    if (i < N) {
-      acc = f30_mac<Chain>(a.v[i], b.v[0], acc);
-      m[i] = sext30((uint32_t)acc * PINV30);
-      acc += (int64_t)m[i] * P30[0];
-    } else {
-      r.v[i - N] = sext30((uint32_t)acc);
-      acc += (int64_t)1 << 29;
-    }
-    acc >>= 30;
-  }
+    for (int j = 0; j < nc; j++) x[n + j] = c.v[j0 + j], y[n + j] = c2[i - j0 - j];
+    if constexpr (sq) x[n + nc] = y[n + nc] = c.v[i / 2];
+    if constexpr (i < N) x[n + nc + sq] = a.v[i], y[n + nc + sq] = b.v[0];
+    acc = f30_column<i, n + nc + sq + (i < N)>(x, y, acc, m, r);
+  });
   r.v[N - 1] = (int32_t)acc;
 }
 // Digit-wise forms: signed digits need no borrowed multiple of p, so a difference or a negation is
@@ -1107,7 +968,6 @@ constexpr bool bls_sqrt_table_is(const int16_t (&e)[8]) {
     if (e[k] != want[k]) return false;
   return true;
 }
-template <bool Chain = true>
 KZG_DEV void fp_pow_pm3d4_30(fp& r, const fp& a_in) {
   typedef uint32_t v8u __attribute__((ext_vector_type(8)));
   static_assert(BlsFp::SQRT_TABLE == 8, "table held as one 8-wide register vector per limb");
@@ -1120,26 +980,26 @@ KZG_DEV void fp_pow_pm3d4_30(fp& r, const fp& a_in) {
   f30 a, a2, a4, t, u;
   f30_from_fp(a, a_in);
   put(0, a);              // a
-  f30_sqr<Chain>(a2, a);         // a^2
-  f30_mul<Chain>(t, a, a2);      // a^3
+  f30_sqr(a2, a);         // a^2
+  f30_mul(t, a, a2);      // a^3
   put(1, t);
-  f30_sqr<Chain>(a4, a2);        // a^4
-  f30_mul<Chain>(t, t, a4);      // a^7
+  f30_sqr(a4, a2);        // a^4
+  f30_mul(t, t, a4);      // a^7
   put(2, t);
-  f30_mul<Chain>(t, t, a2);      // a^9
+  f30_mul(t, t, a2);      // a^9
   put(3, t);
-  f30_mul<Chain>(t, t, a2);      // a^11
+  f30_mul(t, t, a2);      // a^11
   put(4, t);
-  f30_mul<Chain>(t, t, a2);      // a^13
+  f30_mul(t, t, a2);      // a^13
   put(5, t);
-  f30_sqr<Chain>(a4, a4);        // a^8
-  f30_mul<Chain>(u, t, a4);      // a^21
+  f30_sqr(a4, a4);        // a^8
+  f30_mul(u, t, a4);      // a^21
   put(6, u);
-  f30_mul<Chain>(t, t, a2);      // a^15
+  f30_mul(t, t, a2);      // a^15
   u = t;
 #pragma unroll 1
-  for (int k = 0; k < 4; k++) f30_sqr<Chain>(u, u);  // a^240
-  f30_mul<Chain>(u, u, t);       // a^255
+  for (int k = 0; k < 4; k++) f30_sqr(u, u);  // a^240
+  f30_mul(u, u, t);       // a^255
   put(7, u);
   f30 acc;
 #pragma unroll
@@ -1150,16 +1010,16 @@ KZG_DEV void fp_pow_pm3d4_30(fp& r, const fp& a_in) {
     const int nsq = sched_nsq(step), idx = sched_idx(step);
     step = kSqrtSchedule<BlsFp>.step[s + 1];  // in flight during this step's squarings
 #pragma unroll 1
-    for (int k = 0; k < nsq; k++) f30_sqr<Chain>(acc, acc);
+    for (int k = 0; k < nsq; k++) f30_sqr(acc, acc);
     if (idx >= 0) {
 #pragma unroll
       for (int k = 0; k < N30; k++) t.v[k] = (int32_t)tab[k][idx];
-      f30_mul<Chain>(acc, acc, t);
+      f30_mul(acc, acc, t);
     }
   }
 #pragma unroll
   for (int k = 0; k < N30; k++) t.v[k] = POW30_OUT[k];
-  f30_mul<Chain>(acc, acc, t);
+  f30_mul(acc, acc, t);
   fp_from_f30(r, acc);
 }
 
@@ -1210,9 +1070,9 @@ KZG_DEV void fp_pow_pm3d4_window(Fe<Tr>& r, const Fe<Tr>& a) {
 }
 // a^((p-3)/4) for either field: BLS12-381 on the radix-2^30 core with its own table, BN254 by
 // the sliding window above
-template <bool Chain = true, class Tr>
+template <class Tr>
 KZG_DEV void fp_pow_pm3d4(Fe<Tr>& r, const Fe<Tr>& a) {
-  if constexpr (__is_same(Tr, BlsFp)) fp_pow_pm3d4_30<Chain>(r, a);
+  if constexpr (__is_same(Tr, BlsFp)) fp_pow_pm3d4_30(r, a);
   else fp_pow_pm3d4_window(r, a);
 }
 

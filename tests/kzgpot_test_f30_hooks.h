@@ -26,11 +26,6 @@ extern "C" {
 #define KZGPOT_F30_NORM1 7
 #define KZGPOT_F30_NORM2 8
 #define KZGPOT_F30_NORM3 9
-/* MUL, SQR, MUL_ADDSQR with the compiler's column chains (f30_*<false>, the G2 codec's square root)
- * instead of the one serial chain per column: the same digits */
-#define KZGPOT_F30_MUL_C 10
-#define KZGPOT_F30_SQR_C 11
-#define KZGPOT_F30_MUL_ADDSQR_C 12
 int kzgpot_test_f30_op(int op, long n, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d,
                        int32_t* r);
 #ifdef __cplusplus

@@ -1,5 +1,5 @@
-"""The serial-chain forms of the radix-2^30 core (csrc/fp381.hpp f30_mul<true>, f30_sqr<true>,
-f30_mul_addsqr<true>) write a column's mads out by hand, a run of them to one asm statement. A product
+"""The serial-chain forms of the radix-2^30 core (csrc/fp381.hpp f30_mul, f30_sqr, f30_mul_addsqr)
+write a column's mads out by hand, a run of them to one asm statement. A product
 that such a string drops, doubles or takes from the wrong digit shows in tests/test_gpu_f30_core.py
 only as a wrong random digit; here every product slot is the ONLY non-zero product of some lane, so a
 slip names its own slot (j, k):

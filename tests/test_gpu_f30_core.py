@@ -31,15 +31,11 @@ N = 13
 E = (1 << 29) + 4
 TOP = 1 << 23
 LANES = [256, 320]
-# KZGPOT_F30_* (tests/kzgpot_test_f30_hooks.h); _C: the same function with the compiler's column chains
-# (f30_*<false>, the G2 codec's square root) instead of one serial chain per column
-MUL, SQR, MUL_ADDSQR, MUL_SUM2, DBL, MUL3, NORM0, NORM1, NORM2, NORM3, MUL_C, SQR_C, MUL_ADDSQR_C = range(13)
-ARITY = {MUL: 2, SQR: 1, MUL_ADDSQR: 3, MUL_SUM2: 4, DBL: 1, MUL3: 1, NORM0: 1, NORM1: 1, NORM2: 1, NORM3: 1, MUL_C: 2,
-         SQR_C: 1, MUL_ADDSQR_C: 3}
+# KZGPOT_F30_* (tests/kzgpot_test_f30_hooks.h)
+MUL, SQR, MUL_ADDSQR, MUL_SUM2, DBL, MUL3, NORM0, NORM1, NORM2, NORM3 = range(10)
+ARITY = {MUL: 2, SQR: 1, MUL_ADDSQR: 3, MUL_SUM2: 4, DBL: 1, MUL3: 1, NORM0: 1, NORM1: 1, NORM2: 1, NORM3: 1}
 NAMES = {MUL: "f30_mul", SQR: "f30_sqr", MUL_ADDSQR: "f30_mul_addsqr", MUL_SUM2: "f30_mul_sum2", DBL: "f30_dbl",
-         MUL3: "f30_mul3", NORM0: "f30_norm<0>", NORM1: "f30_norm<1>", NORM2: "f30_norm<2>", NORM3: "f30_norm<3>",
-         MUL_C: "f30_mul<false>", SQR_C: "f30_sqr<false>", MUL_ADDSQR_C: "f30_mul_addsqr<false>"}
-SAME_AS = {MUL_C: MUL, SQR_C: SQR, MUL_ADDSQR_C: MUL_ADDSQR}  # the same operands, the same digits
+         MUL3: "f30_mul3", NORM0: "f30_norm<0>", NORM1: "f30_norm<1>", NORM2: "f30_norm<2>", NORM3: "f30_norm<3>"}
 
 
 def _alt(s):
@@ -122,7 +118,6 @@ _cases = {}
 
 def cases(op):
     """(operand tuples, expected digits) for max(LANES) lanes, computed once per op"""
-    op = SAME_AS.get(op, op)
     if op not in _cases:
         ops = operands(op, max(LANES))
         _cases[op] = (ops, [expected(op, o) for o in ops])
@@ -171,7 +166,6 @@ def test_operands_inside_the_model(op):
     """every operand set passes the models' int64 / int32 checks, and the products are the right
     residues with balanced lower digits (needs no GPU)"""
     ops, want = cases(op)
-    op = SAME_AS.get(op, op)
     assert len(ops) == max(LANES)
     for o, r in zip(ops, want):
         v = [L.val(x) for x in o]

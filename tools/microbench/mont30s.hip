@@ -156,9 +156,8 @@ using kzgpot::fp;
 constexpr int N28 = kzgpot::NL;
 
 // V: 0 fp_mul (14 x 28), 1 fp_sqr (14 x 28), 2 mul30, 3 sqr30, 4 / 5 the same with the upper columns
-// chained; 6 ... 11 the codec's own serial-chain forms, kzgpot::f30_mul<true, B> (even V) and
-// f30_sqr<true, B> (odd V) with B = (V - 6) / 2: one mad to an asm statement, a b / m p pairs to a
-// statement, whole runs to a statement (fp381.hpp F30_SINGLE, F30_PAIRS, F30_RUNS).
+// chained; 6 / 7 the codec's kzgpot::f30_mul / f30_sqr (fp381.hpp: one serial mad chain per column,
+// whole runs to an asm statement).
 // CH independent chains per lane.
 template <int V, int CH>
 __global__ void __launch_bounds__(256) kbench(uint32_t* out, const uint32_t* in, int iters, int lds_pad) {
@@ -186,7 +185,6 @@ __global__ void __launch_bounds__(256) kbench(uint32_t* out, const uint32_t* in,
 #pragma unroll
       for (int j = 0; j < N28; j++) s += x[c].v[j] * (j + 1);
   } else if constexpr (V >= 6) {
-    constexpr int B = (V - 6) / 2;
     kzgpot::f30 x[CH], y;
 #pragma unroll
     for (int j = 0; j < N30; j++) {
@@ -200,8 +198,8 @@ __global__ void __launch_bounds__(256) kbench(uint32_t* out, const uint32_t* in,
     for (int it = 0; it < iters; it++) {
 #pragma unroll
       for (int c = 0; c < CH; c++) {
-        if (V & 1) kzgpot::f30_sqr<true, B>(x[c], x[c]);
-        else kzgpot::f30_mul<true, B>(x[c], x[c], y);
+        if (V & 1) kzgpot::f30_sqr(x[c], x[c]);
+        else kzgpot::f30_mul(x[c], x[c], y);
       }
     }
 #pragma unroll
@@ -238,16 +236,7 @@ __global__ void __launch_bounds__(256) kbench(uint32_t* out, const uint32_t* in,
 }
 
 // correctness dump: 256 lanes, a (13 limbs), b, a*b, a^2; then the chained variants' a*b, a^2; then
-// those of f30_mul / f30_sqr<true, B> for B = 0, 1, 2
-template <int B>
-__device__ void check_blocks(int32_t* out, const int32_t (&a)[N30], const int32_t (&b)[N30]) {
-  kzgpot::f30 x, y, r;
-  for (int j = 0; j < N30; j++) x.v[j] = a[j], y.v[j] = b[j];
-  kzgpot::f30_mul<true, B>(r, x, y);
-  for (int j = 0; j < N30; j++) out[j] = r.v[j];
-  kzgpot::f30_sqr<true, B>(r, x);
-  for (int j = 0; j < N30; j++) out[13 + j] = r.v[j];
-}
+// those of the codec's f30_mul / f30_sqr
 __global__ void kcheck30(int32_t* out, const int32_t* in) {
   const int t = threadIdx.x;
   int32_t a[N30], b[N30], r[N30];
@@ -260,9 +249,12 @@ __global__ void kcheck30(int32_t* out, const int32_t* in) {
   mul30c(r2, a, b);
   sqr30c(r, a);
   for (int j = 0; j < N30; j++) out[256 * 52 + t * 26 + j] = r2[j], out[256 * 52 + t * 26 + 13 + j] = r[j];
-  check_blocks<0>(out + 256 * 78 + t * 26, a, b);
-  check_blocks<1>(out + 256 * 104 + t * 26, a, b);
-  check_blocks<2>(out + 256 * 130 + t * 26, a, b);
+  kzgpot::f30 x, y, z;
+  for (int j = 0; j < N30; j++) x.v[j] = a[j], y.v[j] = b[j];
+  kzgpot::f30_mul(z, x, y);
+  for (int j = 0; j < N30; j++) out[256 * 78 + t * 26 + j] = z.v[j];
+  kzgpot::f30_sqr(z, x);
+  for (int j = 0; j < N30; j++) out[256 * 78 + t * 26 + 13 + j] = z.v[j];
 }
 
 int main(int argc, char** argv) {
@@ -274,7 +266,7 @@ int main(int argc, char** argv) {
   uint64_t s = 0x9e3779b97f4a7c15ULL;
   for (int i = 0; i < 4096; i++) { s = s * 6364136223846793005ULL + 1; hin[i] = (uint32_t)(s >> 32); }
   {  // check inputs: random balanced limbs, plus extreme lanes (every limb at -2^29 or 2^29 - 1)
-    static int32_t cin[256 * 26], cout[256 * 156];
+    static int32_t cin[256 * 26], cout[256 * 104];
     for (int t = 0; t < 256; t++)
       for (int j = 0; j < 26; j++) {
         const int k = j % 13;
@@ -300,12 +292,12 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1;
   CHECK(hipEventCreate(&e0));
   CHECK(hipEventCreate(&e1));
-  const char* nm[12] = {"fp_mul 14x28", "fp_sqr 14x28", "mul30 13x30s", "sqr30 13x30s", "mul30 chained", "sqr30 chained",
-                        "f30_mul single", "f30_sqr single", "f30_mul pairs", "f30_sqr pairs", "f30_mul runs", "f30_sqr runs"};
+  const char* nm[8] = {"fp_mul 14x28",  "fp_sqr 14x28",  "mul30 13x30s",  "sqr30 13x30s",
+                       "mul30 chained", "sqr30 chained", "f30_mul codec", "f30_sqr codec"};
   for (int pass = 0; pass < 2; pass++)
-    for (int v = 0; v < 12; v++)
+    for (int v = 0; v < 8; v++)
       for (int ch = 1; ch <= 2; ch++)
-        // the serial-chain forms at one and two waves per SIMD (the codec's occupancy), the others as before
+        // the codec's forms at one and two waves per SIMD (the codec's occupancy), the others as before
         for (int occ = v < 6 ? 2 : 1; occ <= (v < 6 ? 4 : 2); occ *= 2) {
           // one block (4 waves) to a CU at occ = 1: more than half of the CU's 160 KiB
           const size_t lds = occ == 1 ? 96 * 1024 : (160 * 1024) / occ - 1024;
@@ -322,10 +314,6 @@ int main(int argc, char** argv) {
             if (v == 5) L(5, 1);
             if (v == 6) L(6, 1);
             if (v == 7) L(7, 1);
-            if (v == 8) L(8, 1);
-            if (v == 9) L(9, 1);
-            if (v == 10) L(10, 1);
-            if (v == 11) L(11, 1);
           } else {
             if (v == 0) L(0, 2);
             if (v == 1) L(1, 2);
@@ -335,10 +323,6 @@ int main(int argc, char** argv) {
             if (v == 5) L(5, 2);
             if (v == 6) L(6, 2);
             if (v == 7) L(7, 2);
-            if (v == 8) L(8, 2);
-            if (v == 9) L(9, 2);
-            if (v == 10) L(10, 2);
-            if (v == 11) L(11, 2);
           }
 #undef L
           CHECK(hipEventRecord(e1));

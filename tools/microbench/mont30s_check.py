@@ -1,6 +1,6 @@
 """Checks the balanced 13 x 30-bit Montgomery multiply/square dump of mont30s.hip:
-r 2^390 == a b (mod p), output limbs balanced; the three statement cuts of the codec's serial-chain
-forms (one mad, pairs, runs) give the same digits as one another."""
+r 2^390 == a b (mod p), output limbs balanced, for the local baselines, their chained variants and the
+codec's f30_mul / f30_sqr (csrc/fp381.hpp)."""
 import struct
 import sys
 
@@ -29,14 +29,11 @@ def main(path):
         for r, want in ((ext[0:13], val(a) * val(b)), (ext[13:26], val(a) * val(a))):
             if (val(r) * R - want) % P != 0 or not all(-(1 << 29) <= x < (1 << 29) for x in r[:12]):
                 bad += 1
-        forms = [words[256 * (78 + 26 * f) + t * 26:256 * (78 + 26 * f) + t * 26 + 26] for f in range(3)]
-        for f in forms:
-            for r, want in ((f[0:13], val(a) * val(b)), (f[13:26], val(a) * val(a))):
-                if (val(r) * R - want) % P != 0 or not all(-(1 << 29) <= x < (1 << 29) for x in r[:12]):
-                    bad += 1
-            if f != forms[0]:
+        f = words[256 * 78 + t * 26:256 * 78 + t * 26 + 26]
+        for r, want in ((f[0:13], val(a) * val(b)), (f[13:26], val(a) * val(a))):
+            if (val(r) * R - want) % P != 0 or not all(-(1 << 29) <= x < (1 << 29) for x in r[:12]):
                 bad += 1
-    print(f"mont30s check: {bad} mismatches over {10 * lanes} products")
+    print(f"mont30s check: {bad} mismatches over {6 * lanes} products")
     return 1 if bad else 0
 
 
