@@ -481,6 +481,92 @@ int kzgpot_g1_kzg_open_evals_dev(const void* d_lagrange, const void* d_evals, ui
 int kzgpot_g1_kzg_open_evals(const uint8_t* lagrange, const uint8_t* evals, uint32_t exp, const uint8_t z_le32[32],
                              uint8_t out[128], uint32_t flags, int64_t* first_bad);
 
+/* ---------------------------------------------------------------- pairing product, KZG10 check / batch_check */
+/* The functions of this section that verify something return 1 (the product is one / the proofs are
+ * accepted) or 0 (it is not / they are rejected) where the rest of the library returns 0 for success;
+ * a negative value is an error as everywhere else: -(status) for a malformed record, with its index in
+ * *first_bad, and <= KZGPOT_E_INVALID_ARG for argument and device errors.
+ *
+ * Pairing product: prod_{i < k} e(P_i, Q_i)^d over BLS12-381, e the optimal ate pairing and
+ * d = KZGPOT_PAIRING_GT_POWER. The tower is ark-bls12-381's: Fq2 = Fq[u]/(u^2 + 1),
+ * Fq6 = Fq2[v]/(v^3 - (u + 1)), Fq12 = Fq6[w]/(w^2 - v); the twist is of M type; the Miller loop runs
+ * over |x| = 0xd201000000010000 and its value is conjugated for the negative x. One lane runs the
+ * Miller loop of one pair, the lanes' values are multiplied by a tree, and ONE final exponentiation is
+ * applied to the product.
+ *   d          The hard part of the final exponentiation computes f^(3 (p^4 - p^2 + 1) / r), so the GT
+ *              value is the CUBE of the reduced pairing f^((p^12 - 1) / r): d = 3. r is prime and not 3,
+ *              so the product is one for d = 3 exactly when it is for d = 1, and the booleans of this
+ *              section do not depend on d. The GT bytes do: they are e(P, Q)^3 by the mathematical
+ *              definition. No byte equality with ark's Bls12_381::pairing is claimed.
+ *   g1, g2     k ark-uncompressed G1 records (96 B) and G2 records (192 B). Both are range- and
+ *              flag-checked as the MSM checks its bases (status 3 or 6), the index counting along g1
+ *              then g2: i < k is g1[i], otherwise g2[i - k]; the smallest is reported and a rejected
+ *              call writes nothing. A record with the infinity flag, on either side, is legal and its
+ *              pair contributes 1. Points are NOT checked for curve or subgroup membership: as for the
+ *              MSM, the result is defined for points of the prime-order subgroups (decode through
+ *              the checked codecs).
+ *   out_gt     KZGPOT_GT_BYTES bytes, or NULL: the product in ark's serialization order of Fq12,
+ *              c0.c0.c0, c0.c0.c1, c0.c1.c0, .., c1.c2.c1, each 48 little-endian bytes, canonical.
+ *   k          at most KZGPOT_PAIRING_MAX_PAIRS (the work is one lane per pair); k = 0 gives one.
+ * k above the cap or a NULL pointer where k is non-zero is KZGPOT_E_INVALID_ARG before any device use,
+ * and the workspace function then returns 0. */
+#define KZGPOT_PAIRING_GT_POWER 3
+#define KZGPOT_PAIRING_MAX_PAIRS 65536u
+#define KZGPOT_GT_BYTES 576
+/* Host only. Bytes of device memory (d_work) for k pairs: 3,248 per pair (a lane's 29 Fq2 cells), in
+ * blocks of 64 pairs, and 6,400 for the final exponentiation; monotone in k; 0 for k above the cap. */
+uint64_t kzgpot_pairing_workspace(uint64_t k);
+/* Asynchronous on `stream`: every d_ pointer in HBM and 16-byte aligned. d_out: KZGPOT_GT_BYTES of GT,
+ * then one u32 that is 1 if the product is one and 0 if not (580 bytes). d_bad_key as for
+ * kzgpot_g1_msm_dev; d_out is written only if it reports no rejection. Returns 0 or an error. */
+int kzgpot_pairing_product_dev(const void* d_g1, const void* d_g2, uint64_t k, void* d_out, void* d_work,
+                               uint64_t* d_bad_key, void* stream);
+/* The same on host buffers, synchronous, on the current device: 1 if the product is one, 0 if not. */
+int kzgpot_pairing_product(const uint8_t* g1, const uint8_t* g2, uint64_t k, uint8_t* out_gt, int64_t* first_bad);
+
+/* KZG10 batch_check: ark-poly-commit 0.2's KZG10::batch_check over n proofs with the randomizers rho_i
+ * supplied by the caller (ark takes rho_0 = 1 and draws every later one as a u128 from the caller's
+ * rng; this library never draws randomness itself):
+ *   total_c = sum_i [rho_i] (C_i + [z_i] W_i) - [sum_i rho_i v_i] g - [sum_i rho_i vbar_i] gamma_g
+ *   total_w = sum_i [rho_i] W_i
+ *   accepted iff  e(total_c, h) e(-total_w, beta_h) = 1
+ * An Fr pass writes the scalars rho_i, rho_i z_i and the two negated sums; total_c is ONE multi-scalar
+ * multiplication over commitments, proofs, g, gamma_g (2 n + 2 bases, staged end to end), total_w a
+ * second one over the proofs where they lie; the pairing product above runs over the two pairs. The
+ * scalars and both sums never leave device memory.
+ *   vk            g, gamma_g (96 B each), h, beta_h (192 B each), ark-uncompressed: 576 bytes
+ *   commitments, proofs_w   n ark-uncompressed G1 records each
+ *   points, values, random_vs, randomizers   n x 32 little-endian bytes each, every one any 256-bit
+ *                 integer, reduced mod r. random_vs may be NULL: no proof is hiding (every vbar_i = 0).
+ *   flags         KZGPOT_MSM_WINDOW(c) only
+ *   first_bad     counts along commitments, proofs, then the four vk records: i < n is commitments[i],
+ *                 i < 2 n is proofs_w[i - n], then g, gamma_g, h, beta_h. Records are checked as the
+ *                 MSM and the pairing product check theirs; points are not checked for subgroup
+ *                 membership.
+ * n = 0 is accepted, as ark's empty product is. n <= 2^25 - 1, so that 2 n + 2 stays within what the
+ * MSM takes; above that, a NULL pointer where n is non-zero (random_vs excepted), a NULL vk or an
+ * unknown flag bit is KZGPOT_E_INVALID_ARG before any device use, and the workspace function returns 0.
+ *
+ * KZG10 check is the batch call with n = 1 and rho = 1: ark's equation
+ * e(C - [v] g - [vbar] gamma_g, h) = e(W, beta_h - [z] h) with [z] W moved to the left-hand side,
+ * e(C + [z] W - [v] g - [vbar] gamma_g, h) e(-W, beta_h) = 1, which needs no G2 scalar multiplication. */
+/* Host only. Bytes of d_work for n proofs; monotone in n; 0 when the arguments are invalid. */
+uint64_t kzgpot_kzg_batch_check_workspace(uint64_t n, uint32_t flags);
+/* Asynchronous on `stream`: every d_ pointer in HBM and 16-byte aligned (d_vk: the 576 bytes above;
+ * d_random_vs may be NULL). d_out as for kzgpot_pairing_product_dev: the GT value of the check's
+ * product, then the u32 that is 1 if the proofs are accepted. d_bad_key as for kzgpot_g1_msm_dev.
+ * Returns 0 or an error. */
+int kzgpot_kzg_batch_check_dev(const void* d_vk, const void* d_commitments, const void* d_points, const void* d_values,
+                               const void* d_proofs_w, const void* d_random_vs, const void* d_randomizers, uint64_t n,
+                               void* d_out, uint32_t flags, void* d_work, uint64_t* d_bad_key, void* stream);
+/* The same on host buffers, synchronous, on the current device: 1 accepted, 0 rejected. */
+int kzgpot_kzg_batch_check(const uint8_t vk[576], const uint8_t* commitments, const uint8_t* points,
+                           const uint8_t* values, const uint8_t* proofs_w, const uint8_t* random_vs,
+                           const uint8_t* randomizers, uint64_t n, uint32_t flags, int64_t* first_bad);
+/* One proof: random_v_le32 may be NULL (not hiding). first_bad: 0 the commitment, 1 w, 2 .. 5 the vk records. */
+int kzgpot_kzg_check(const uint8_t vk[576], const uint8_t commitment[96], const uint8_t z_le32[32],
+                     const uint8_t value_le32[32], const uint8_t w[96], const uint8_t* random_v_le32, int64_t* first_bad);
+
 /* ---------------------------------------------------------------- BN254 (config 5, next-row §8f 4) */
 /* No reference counterpart: the same path instantiated for ark-bn254 0.2 G1 (cofactor 1).
  * ark compressed (32 B: x LE, SWFlags bit7 PositiveY / bit6 Infinity in byte 31) → ark

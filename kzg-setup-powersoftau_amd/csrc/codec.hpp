@@ -125,6 +125,20 @@ hipError_t launch_evals_divide(const EvalPlan& p, const void* d_evals, const fr_
 // the open's last step: the value (32 B) behind the proof's point, unless the MSM's load rejected a base
 hipError_t launch_evals_emit(const void* d_value, void* d_out32, const unsigned long long* d_key, hipStream_t stream);
 
+// pairing product (pairing_kernels.hip): d_out (576 B of GT, then one u32: 1 if it is one) =
+// prod_{i < k} e(g1[i], g2[i])^KZGPOT_PAIRING_GT_POWER over ark records; k <= kPairMaxK. A malformed
+// record lowers d_key to (key_bias + its index along g1 then g2) << 8 | status, and nothing is written
+// once d_key reports a rejection, this call's or an earlier one's. d_work: pairing_workspace_bytes, laid
+// out by pairing_plan (plans.hpp).
+hipError_t launch_pairing_product(const void* d_g1, const void* d_g2, uint64_t k, void* d_out, void* d_work,
+                                  unsigned long long* d_key, uint64_t key_bias, hipStream_t stream);
+
+// KZG10 check (verify_kernels.hip). The Fr pass: the scalar rows rho_i, rho_i z_i and the two negated
+// sums into the plan's `scalars` (d_random_vs may be null); and the negation of one ark G1 record in place.
+hipError_t launch_check_scalars(const CheckPlan& p, const void* d_randomizers, const void* d_points, const void* d_values,
+                                const void* d_random_vs, void* d_work, hipStream_t stream);
+hipError_t launch_g1_negate(void* d_record, hipStream_t stream);
+
 // Fr NTT (ntt_kernels.hip). The scalars of one transform, computed on the host (domain.hip) with
 // csrc/fr.hpp. d_tw: the plan's twiddle tables (tw_bytes); d_stage: the plan's staging array
 // (stage_bytes), needed only where d_out is d_in and the plan has more than one pass. d_key

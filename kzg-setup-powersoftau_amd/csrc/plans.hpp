@@ -1,7 +1,8 @@
 // The launch plans of the group FFT (fft_kernels.hip), the multi-scalar multiplication
 // (msm_kernels.hip), the polynomial division (poly_kernels.hip), KZG10 open (open.hip), the Fr NTT
-// (ntt_kernels.hip), the amortized openings over a domain (domain.hip) and the evaluation form
-// (eval_kernels.hip, evals.hip), each stated once: where every kernel reads and writes inside the
+// (ntt_kernels.hip), the amortized openings over a domain (domain.hip), the evaluation form
+// (eval_kernels.hip, evals.hip), the pairing product (pairing_kernels.hip) and KZG10 check /
+// batch_check (verify.hip), each stated once: where every kernel reads and writes inside the
 // caller-supplied workspace, and the launch schedule as data (one entry per stage, level or step, in
 // launch order). The launchers run the tables; nothing else decides an offset or a lane count.
 //
@@ -9,7 +10,8 @@
 // (tests/host_units/plan_units.cpp, built by g++ with and without sanitizers; tests/test_plan_units.py
 // checks every launch's reads and writes against its regions; tests/host_units/ntt_units.cpp and
 // tests/test_ntt_units.py do the same for the NTT's and the domain's plans,
-// tests/host_units/eval_units.cpp and tests/test_eval_units.py for the evaluation form's).
+// tests/host_units/eval_units.cpp and tests/test_eval_units.py for the evaluation form's,
+// tests/host_units/verify_units.cpp and tests/test_verify_units.py for the pairing's and the check's).
 #pragma once
 #include <stdint.h>
 
@@ -356,6 +358,79 @@ inline OpenEvalsPlan open_evals_plan(uint32_t exp, uint32_t flags) {
   p.ok = true;
   return p;
 }
+
+// ---------------------------------------------------------------- pairing product (pairing_kernels.hip)
+// One lane per pair. A lane's state is kPairLaneCells cells of one Fq2 (28 words) each, word-major
+// across `stride` lanes (the pair count rounded up to the Miller kernel's block), followed by the
+// kPairFinalCells cells of the one lane that runs the final exponentiation. The product tree is one
+// k_pair_tree launch per level: `count` live values `step` lanes apart, 256 of them per block.
+constexpr uint64_t kPairMaxK = KZGPOT_PAIRING_MAX_PAIRS;
+constexpr uint32_t kPairMillerBlock = 64, kPairLaneCells = 29, kPairFinalCells = 56, kPairCellBytes = 112;
+constexpr uint32_t kPairMaxLevels = 2;
+static_assert(256ull * 256 >= kPairMaxK, "level[] holds every level of the largest product");
+struct PairLevel {
+  uint64_t count, step;
+  uint32_t blocks;
+};
+struct PairingPlan {
+  uint64_t k, stride;
+  uint64_t lanes, final_cells, bytes;  // byte offsets; bytes = 0: invalid arguments
+  uint32_t nlevels;
+  PairLevel level[kPairMaxLevels];
+  bool ok;
+};
+inline PairingPlan pairing_plan(uint64_t k) {
+  PairingPlan p = {};
+  if (k > kPairMaxK) return p;
+  p.k = k;
+  p.stride = (uint64_t)grid_for(k, kPairMillerBlock) * kPairMillerBlock;
+  uint64_t o = 0;
+  p.lanes = o, o += align256(p.stride * kPairLaneCells * kPairCellBytes);
+  p.final_cells = o, o += align256((uint64_t)kPairFinalCells * kPairCellBytes);
+  p.bytes = o;
+  for (uint64_t count = k, step = 1; count > 1; count = (count + 255) / 256, step *= 256)
+    p.level[p.nlevels++] = PairLevel{count, step, grid_for(count, 256)};
+  p.ok = true;
+  return p;
+}
+inline uint64_t pairing_workspace_bytes(uint64_t k) { return pairing_plan(k).bytes; }
+
+// ---------------------------------------------------------------- KZG10 check and batch_check (verify.hip)
+// n proofs. Workspace: the one MSM's bases end to end (commitments, proofs, g, gamma_g: 2 n + 2
+// records), its scalars (rho_i, rho_i z_i, -sum rho_i v_i, -sum rho_i vbar_i), the Fr pass's partial
+// sums (two per block of 256), the pairing product's two pairs (total_c and -total_w, then h and
+// beta_h), a key of its own for the second MSM (over the proofs where they lie in `bases`; the first
+// MSM has checked the same records under their indices), the MSMs' workspace, the pairing's.
+constexpr uint64_t kCheckMaxN = (1ull << 25) - 1;
+constexpr uint32_t kCheckFlags = KZGPOT_MSM_WINDOW(0x1f);
+struct CheckPlan {
+  uint64_t n, nbases, blocks;
+  uint32_t c;  // the width override, 0 for the library's
+  uint64_t bases, scalars, sums, pairs_g1, pairs_g2, key2, msm, pairing, bytes;  // byte offsets
+  bool ok;
+};
+inline CheckPlan check_plan(uint64_t n, uint32_t flags) {
+  CheckPlan p = {};
+  if (n > kCheckMaxN || (flags & ~kCheckFlags) || !msm_window_flag(flags, p.c)) return p;
+  p.n = n;
+  p.nbases = 2 * n + 2;
+  p.blocks = grid_for(n, 256);
+  const uint64_t msm_bytes = msm_workspace_bytes(false, p.nbases, p.c);
+  if (!msm_bytes) return p;
+  uint64_t o = 0;
+  p.bases = o, o += align256(p.nbases * point_record(false));
+  p.scalars = o, o += align256(p.nbases * 32);
+  p.sums = o, o += align256(2 * p.blocks * 32);
+  p.pairs_g1 = o, o += align256(2 * point_record(false));
+  p.pairs_g2 = o, o += align256(2 * point_record(true));
+  p.key2 = o, o += 256;
+  p.msm = o, o += msm_bytes;
+  p.pairing = o, o += pairing_workspace_bytes(2);
+  p.bytes = o;
+  p.ok = true;
+  return p;
+}
+inline uint64_t check_workspace_bytes(uint64_t n, uint32_t flags) { return check_plan(n, flags).bytes; }
 
 // ---------------------------------------------------------------- Fr NTT
 // A transform of m = 2^exp elements in passes (ntt_kernels.hip): a block of 256 lanes holds

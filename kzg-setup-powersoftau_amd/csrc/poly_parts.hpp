@@ -57,5 +57,55 @@ __device__ inline void stage_in(uint4* tile, const uint4* in, uint64_t blk, uint
   }
 }
 
+// ---------------------------------------------------------------- sums over a block, entries in HBM
+// (eval_kernels.hip: the division in evaluation form; verify_kernels.hip: the check's Fr pass)
+__device__ inline fr fr_zero() { return fr{{0, 0, 0, 0, 0, 0, 0, 0}}; }
+
+// the sum of the 256 lanes' acc -> lane 0's acc (rows is free on entry and on return)
+__device__ inline void block_sum(fr& acc, uint32_t (*rows)[256]) {
+  const uint32_t tid = threadIdx.x;
+  park(rows, tid, acc);
+#pragma unroll 1
+  for (int k = 0; k < 8; k++) {
+    const uint32_t live = 128u >> k;
+    __syncthreads();
+    fr lo, hi;
+    if (tid < live) {
+      unpark(lo, rows, 2 * tid);
+      unpark(hi, rows, 2 * tid + 1);
+    }
+    __syncthreads();
+    if (tid < live) {
+      fr_add(acc, lo, hi);
+      park(rows, tid, acc);
+    }
+  }
+  __syncthreads();
+}
+
+__device__ inline void load_entry(fr& a, const uint4* v, uint64_t i) {  // any 256-bit integer -> Montgomery
+  const uint4 lo = v[2 * i], hi = v[2 * i + 1];
+  a = fr{{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}};
+  fr_load(a, a);
+}
+__device__ inline void words_out(uint32_t* out, const fr& a) {
+#pragma unroll
+  for (int k = 0; k < 8; k++) out[k] = a.v[k];
+}
+__device__ inline void words_in(fr& a, const uint32_t* in) {
+#pragma unroll
+  for (int k = 0; k < 8; k++) a.v[k] = in[k];
+}
+// the sum of `count` entries of 8 words -> lane 0's acc
+__device__ inline void sum_entries(fr& acc, const uint32_t* __restrict__ v, uint64_t count, uint32_t (*rows)[256]) {
+  acc = fr_zero();
+  for (uint64_t t = threadIdx.x; t < count; t += 256) {
+    fr a;
+    words_in(a, v + t * 8);
+    fr_add(acc, acc, a);
+  }
+  block_sum(acc, rows);
+}
+
 }  // namespace
 }  // namespace kzgpot

@@ -1,0 +1,115 @@
+// C ABI (include/kzgpot.h): ark-poly-commit's KZG10::check and KZG10::batch_check — the Fr pass and
+// the negation by verify_kernels.hip, total_c and total_w by two launch_msm (msm_kernels.hip), the
+// product of the two pairings by launch_pairing_product (pairing_kernels.hip). The scalars, both sums
+// and both points never leave HBM. The workspace is check_plan's (plans.hpp).
+#include <string.h>
+
+#include "codec.hpp"
+#include "device_rt.hpp"
+#include "host_rt.hpp"
+
+using namespace kzgpot;
+
+namespace {
+
+constexpr uint64_t kG1 = point_record(false), kG2 = point_record(true);
+constexpr uint64_t kVkBytes = 2 * kG1 + 2 * kG2, kOutBytes = KZGPOT_GT_BYTES + 4;
+static_assert(kVkBytes == 576, "g, gamma_g, h, beta_h");
+
+// host_key (optional): receives the bad key once the check is done
+int check_dev(const void* d_vk, const void* d_commitments, const void* d_points, const void* d_values,
+              const void* d_proofs_w, const void* d_random_vs, const void* d_randomizers, uint64_t n, void* d_out,
+              uint32_t flags, void* d_work, uint64_t* d_bad_key, void* stream, uint64_t* host_key = nullptr) {
+  const CheckPlan p = check_plan(n, flags);
+  if (!p.ok || !d_vk || !d_out || !d_work || !d_bad_key ||
+      (n && (!d_commitments || !d_points || !d_values || !d_proofs_w || !d_randomizers)))
+    return KZGPOT_E_INVALID_ARG;
+  const hipStream_t s = (hipStream_t)stream;
+  uint8_t* w = (uint8_t*)d_work;
+  uint8_t *bases = w + p.bases, *scalars = w + p.scalars, *total_c = w + p.pairs_g1, *total_w = total_c + kG1;
+  const uint8_t* vk = (const uint8_t*)d_vk;
+  auto width = [&](uint64_t m) { return p.c ? p.c : msm_window_bits(m); };
+  return launch_with_key(d_bad_key, s, [&](unsigned long long* key) -> hipError_t {
+    hipError_t e;
+    if (n && (e = hipMemcpyAsync(bases, d_commitments, n * kG1, hipMemcpyDeviceToDevice, s))) return e;
+    if (n && (e = hipMemcpyAsync(bases + n * kG1, d_proofs_w, n * kG1, hipMemcpyDeviceToDevice, s))) return e;
+    if ((e = hipMemcpyAsync(bases + 2 * n * kG1, vk, 2 * kG1, hipMemcpyDeviceToDevice, s))) return e;  // g, gamma_g
+    if ((e = hipMemcpyAsync(w + p.pairs_g2, vk + 2 * kG1, 2 * kG2, hipMemcpyDeviceToDevice, s))) return e;  // h, beta_h
+    // an MSM that rejects a base writes no point: the pairing's load then reads these zeros, a well-formed record
+    if ((e = hipMemsetAsync(total_c, 0, 2 * kG1, s))) return e;
+    if ((e = hipMemsetAsync(w + p.key2, 0xff, sizeof(uint64_t), s))) return e;
+    if ((e = launch_check_scalars(p, d_randomizers, d_points, d_values, d_random_vs, d_work, s))) return e;
+    // total_w = sum [rho_i] W_i: the proofs where they lie, the first n scalar rows; its rejections (under
+    // the proofs' own indices) go to a key of its own, the next MSM reports the same records under theirs
+    if ((e = launch_msm(false, bases + n * kG1, scalars, n, total_w, false, width(n), w + p.msm,
+                        (unsigned long long*)(w + p.key2), s)))
+      return e;
+    if ((e = launch_msm(false, bases, scalars, p.nbases, total_c, false, width(p.nbases), w + p.msm, key, s))) return e;
+    if ((e = launch_g1_negate(total_w, s))) return e;
+    // e(total_c, h) e(-total_w, beta_h); h and beta_h are records 2 n + 2 and 2 n + 3 of the call
+    return launch_pairing_product(total_c, w + p.pairs_g2, 2, d_out, w + p.pairing, key, 2 * n, s);
+  }, host_key);
+}
+
+int check_host(const uint8_t* vk, const uint8_t* commitments, const uint8_t* points, const uint8_t* values,
+               const uint8_t* proofs_w, const uint8_t* random_vs, const uint8_t* randomizers, uint64_t n, uint32_t flags,
+               int64_t* first_bad) {
+  if (first_bad) *first_bad = -1;
+  const CheckPlan p = check_plan(n, flags);
+  if (!p.ok || !vk || (n && (!commitments || !points || !values || !proofs_w || !randomizers))) return KZGPOT_E_INVALID_ARG;
+  if (device_count() <= 0) return KZGPOT_E_DEVICE;
+  DeviceGuard guard;
+  DevBuf d_vk, d_points, d_scalars, d_out, work, key;
+  // the G1 records end to end (commitments, proofs), the four scalar arrays end to end
+  const uint64_t ns = random_vs ? 4 : 3;
+  if (d_vk.alloc(kVkBytes) || d_points.alloc(2 * n * kG1) || d_scalars.alloc(ns * n * 32) || d_out.alloc(kOutBytes) ||
+      work.alloc(p.bytes) || key.alloc(sizeof(uint64_t)))
+    return KZGPOT_E_DEVICE;
+  uint8_t *dp = (uint8_t*)d_points.p, *ds = (uint8_t*)d_scalars.p;
+  HIP_TRY(hipMemcpy(d_vk.p, vk, kVkBytes, hipMemcpyHostToDevice));
+  if (n) {
+    HIP_TRY(hipMemcpy(dp, commitments, n * kG1, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dp + n * kG1, proofs_w, n * kG1, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ds, points, n * 32, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ds + n * 32, values, n * 32, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ds + 2 * n * 32, randomizers, n * 32, hipMemcpyHostToDevice));
+    if (random_vs) HIP_TRY(hipMemcpy(ds + 3 * n * 32, random_vs, n * 32, hipMemcpyHostToDevice));
+  }
+  uint64_t bad;
+  if (const int r = check_dev(d_vk.p, dp, ds, ds + n * 32, dp + n * kG1, random_vs ? ds + 3 * n * 32 : nullptr,
+                              ds + 2 * n * 32, n, d_out.p, flags, work.p, (uint64_t*)key.p, nullptr, &bad))
+    return r;
+  if (bad != kNoBad) return decode_key(bad, first_bad);
+  uint32_t accepted;
+  HIP_TRY(hipMemcpy(&accepted, (uint8_t*)d_out.p + KZGPOT_GT_BYTES, 4, hipMemcpyDeviceToHost));
+  return accepted ? 1 : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* host only */
+uint64_t kzgpot_kzg_batch_check_workspace(uint64_t n, uint32_t flags) { return check_workspace_bytes(n, flags); }
+int kzgpot_kzg_batch_check_dev(const void* d_vk, const void* d_commitments, const void* d_points, const void* d_values,
+                               const void* d_proofs_w, const void* d_random_vs, const void* d_randomizers, uint64_t n,
+                               void* d_out, uint32_t flags, void* d_work, uint64_t* d_bad_key, void* stream) {
+  return api_guard([&] {
+    return check_dev(d_vk, d_commitments, d_points, d_values, d_proofs_w, d_random_vs, d_randomizers, n, d_out, flags,
+                     d_work, d_bad_key, stream);
+  });
+}
+int kzgpot_kzg_batch_check(const uint8_t vk[576], const uint8_t* commitments, const uint8_t* points,
+                           const uint8_t* values, const uint8_t* proofs_w, const uint8_t* random_vs,
+                           const uint8_t* randomizers, uint64_t n, uint32_t flags, int64_t* first_bad) {
+  return api_guard([&] {
+    return check_host(vk, commitments, points, values, proofs_w, random_vs, randomizers, n, flags, first_bad);
+  });
+}
+int kzgpot_kzg_check(const uint8_t vk[576], const uint8_t commitment[96], const uint8_t z_le32[32],
+                     const uint8_t value_le32[32], const uint8_t w[96], const uint8_t* random_v_le32, int64_t* first_bad) {
+  const uint8_t one[32] = {1};  // rho = 1
+  return api_guard([&] { return check_host(vk, commitment, z_le32, value_le32, w, random_v_le32, one, 1, 0, first_bad); });
+}
+
+}  // extern "C"

@@ -11,6 +11,8 @@ C ABI in `include/kzgpot.h`:
   download_fastkzg_setup       src/lib.rs:166-172   (no network in this build: local file + digest)
   preprocess_kgz /
   preprocess_fastkgz           src/bin/preprocess-{kgz,fastkgz}.rs main
+  kzg_commit / kzg_open /
+  kzg_check / kzg_batch_check  src/lib.rs:250-289   (end_to_end_test_kzg's calls into ark-poly-commit)
 
 Every compute call runs the HIP kernels; errors raise `KzgPotError` (the reference `unwrap()`s
 and panics on the first bad point — preprocess-kgz.rs:110,142).
@@ -867,3 +869,126 @@ def kzg_open_evals(lagrange, evals, exp: int, z, window: int = 0, tile: int = 0)
     monomial powers. Not hiding: `random_v` is None. A malformed record raises KzgPotError."""
     out = _checked(g1_kzg_open_evals(lagrange, evals, exp, z, window=window, tile=tile))
     return KzgProof(out[:96], None, int.from_bytes(out[96:], "little"))
+
+
+# ------------------------------------------------------------------ pairing product, KZG10 check / batch_check
+GT_BYTES = 576
+PAIRING_GT_POWER = 3        # KZGPOT_PAIRING_GT_POWER: the GT bytes are e(P, Q)^3
+PAIRING_MAX_PAIRS = 1 << 16
+VK_BYTES = 576              # g, gamma_g (96 B each), h, beta_h (192 B each), ark-uncompressed
+CHECK_MAX_N = (1 << 25) - 1
+CHECK_SECTIONS = ("commitments", "proofs", "vk")
+
+
+def pairing_workspace(k: int) -> int:
+    return int(_lib.load().kzgpot_pairing_workspace(k))
+
+
+def kzg_batch_check_workspace(n: int, flags: int = 0) -> int:
+    return int(_lib.load().kzgpot_kzg_batch_check_workspace(n, flags))
+
+
+def g1g2_pairing_product(g1_records, g2_records) -> CodecResult:
+    """kzgpot_pairing_product on packed ark-uncompressed records: ret = 1 if the product of the k
+    pairings is one, 0 if not, and `out` the 576 GT bytes; a malformed record gives ret = -(status),
+    first_bad = its index along g1 then g2 and out = b""."""
+    p1, n1, keep1 = _buf(g1_records)
+    p2, n2, keep2 = _buf(g2_records)
+    k = n1 // 96
+    if n1 != 96 * k or n2 != 192 * k:
+        raise ValueError(f"pairing product: {n1} B of G1 records and {n2} B of G2 records")
+    out = ctypes.create_string_buffer(GT_BYTES)
+    fb = ctypes.c_int64(-1)
+    ret = _lib.load().kzgpot_pairing_product(p1 if k else None, p2 if k else None, k, out, ctypes.byref(fb))
+    del keep1, keep2
+    if ret <= -100:
+        raise KzgPotError(ret)
+    return CodecResult(out.raw if ret >= 0 else b"", ret, fb.value, None)
+
+
+def pairing_product(g1_records, g2_records):
+    """(is_one, gt) for prod_i e(P_i, Q_i)^3 over packed ark-uncompressed G1 (96 B) and G2 (192 B)
+    records: `gt` the 576 bytes of the product in ark's Fq12 order. Points are range- and flag-checked,
+    not subgroup-checked; an infinity record contributes 1. A malformed record raises KzgPotError with
+    its index along g1 then g2."""
+    res = g1g2_pairing_product(g1_records, g2_records)
+    if res.ret < 0:
+        raise KzgPotError(res.ret, res.first_bad)
+    return res.ret == 1, res.out
+
+
+def verifier_key_records(vk: VerifierKey) -> bytes:
+    """The 576 packed bytes g ‖ gamma_g ‖ h ‖ beta_h, ark-uncompressed, of a loader's VerifierKey
+    (whose fields are in-memory Montgomery rows): each row through the MSM with the scalar 1."""
+    return b"".join(_checked((g2_msm if g2 else g1_msm)(row, [1], mont=True))
+                    for row, g2 in ((vk.g, False), (vk.gamma_g, False), (vk.h, True), (vk.beta_h, True)))
+
+
+def _vk_bytes(vk) -> bytes:
+    data = verifier_key_records(vk) if isinstance(vk, VerifierKey) else bytes(vk)
+    if len(data) != VK_BYTES:
+        raise ValueError(f"verifier key: {len(data)} B, {VK_BYTES} expected")
+    return data
+
+
+def g1_kzg_batch_check(vk, commitments, points, values, proofs_w, random_vs, randomizers, window: int = 0) -> CodecResult:
+    """kzgpot_kzg_batch_check on packed records and scalars as given: ret = 1 accepted, 0 rejected; a
+    malformed record gives ret = -(status) and first_bad = its index along commitments ‖ proofs ‖ the
+    four vk records. `random_vs` may be None (no proof is hiding)."""
+    c, w = bytes(commitments), bytes(proofs_w)
+    z, v, rho = _scalar_bytes(points), _scalar_bytes(values), _scalar_bytes(randomizers)
+    rv = _scalar_bytes(random_vs) if random_vs is not None else None
+    n = len(c) // 96
+    if len(c) != 96 * n or len(w) != 96 * n or any(len(s) != 32 * n for s in (z, v, rho) + ((rv,) if rv is not None else ())):
+        raise ValueError(f"kzg batch check: buffer sizes do not agree on n = {n}")
+    fb = ctypes.c_int64(-1)
+    arg = lambda b: b if n else None  # noqa: E731
+    ret = _lib.load().kzgpot_kzg_batch_check(_vk_bytes(vk), arg(c), arg(z), arg(v), arg(w), arg(rv) if rv is not None else None,
+                                             arg(rho), n, msm_flags(False, window), ctypes.byref(fb))
+    if ret <= -100:
+        raise KzgPotError(ret)
+    return CodecResult(b"", ret, fb.value, None)
+
+
+def _proof_parts(proof):
+    return (proof.w, proof.random_v) if isinstance(proof, KzgProof) else (bytes(proof), None)
+
+
+def kzg_batch_check(vk, commitments, points, values, proofs, randomizers=None, window: int = 0) -> bool:
+    """ark-poly-commit 0.2 `KZG10::batch_check(&vk, &commitments, &points, &values, &proofs, rng)`:
+    True iff all n proofs verify, by two MSMs and ONE product of two pairings on the GPU. `vk` is a
+    VerifierKey from the loaders or its 576 packed bytes (verifier_key_records); `commitments` ark G1
+    records (a list, or packed bytes), `points` and `values` ints, `proofs` KzgProof objects (hiding
+    ones carry random_v) or bare `w` records. `randomizers` are the n integers that ark draws from its
+    rng: None draws them here as ark does, the first 1 and the others 128 bits from `secrets`; passing
+    them makes the call reproducible. A malformed record raises KzgPotError with its index along
+    commitments ‖ proofs ‖ vk."""
+    import secrets
+
+    comm = bytes(commitments) if isinstance(commitments, (bytes, bytearray, memoryview)) else b"".join(commitments)
+    parts = [_proof_parts(p) for p in proofs]
+    n = len(parts)
+    if randomizers is None:
+        randomizers = [1] + [secrets.randbits(128) for _ in range(n - 1)] if n else []
+    hiding = any(rv is not None for _, rv in parts)
+    res = g1_kzg_batch_check(vk, comm, list(points), list(values), b"".join(w for w, _ in parts),
+                             [rv or 0 for _, rv in parts] if hiding else None, list(randomizers), window=window)
+    if res.ret < 0:
+        raise KzgPotError(res.ret, res.first_bad)
+    return res.ret == 1
+
+
+def kzg_check(vk, commitment, z, value, proof, random_v=None) -> bool:
+    """ark-poly-commit 0.2 `KZG10::check(&vk, &commitment, point, value, &proof)`: True iff `proof`
+    (a KzgProof, or the bare `w` record with `random_v` given here; None: not hiding) shows that the
+    committed polynomial evaluates to `value` at `z`. The batch check with one proof and the
+    randomizer 1. A malformed record raises KzgPotError: index 0 the commitment, 1 w, 2 .. 5 the vk."""
+    w, rv = _proof_parts(proof)
+    if random_v is not None:
+        rv = random_v
+    fb = ctypes.c_int64(-1)
+    ret = _lib.load().kzgpot_kzg_check(_vk_bytes(vk), bytes(commitment), _fr_bytes(z), _fr_bytes(value), bytes(w),
+                                       _fr_bytes(rv) if rv is not None else None, ctypes.byref(fb))
+    if ret < 0:
+        raise KzgPotError(ret, fb.value)
+    return ret == 1

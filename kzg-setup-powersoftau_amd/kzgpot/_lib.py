@@ -93,6 +93,13 @@ SIGNATURES = {
     "kzgpot_kzg_open_evals_workspace": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
     "kzgpot_g1_kzg_open_evals_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "kzgpot_g1_kzg_open_evals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, i64p]),
+    "kzgpot_pairing_workspace": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "kzgpot_pairing_product_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kzgpot_pairing_product": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, i64p]),
+    "kzgpot_kzg_batch_check_workspace": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint32]),
+    "kzgpot_kzg_batch_check_dev": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kzgpot_kzg_batch_check": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_uint64, ctypes.c_uint32, i64p]),
+    "kzgpot_kzg_check": (ctypes.c_int, [ctypes.c_void_p] * 6 + [i64p]),
     "kzgpot_phase1radix_size": (ctypes.c_uint64, [ctypes.c_uint32]),
     "kzgpot_prepare_phase2_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, intp, i64p]),
     "kzgpot_prepare_phase2": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, intp, i64p]),

@@ -383,3 +383,60 @@ def g1_kzg_open_evals_dev(d_lagrange: torch.Tensor, d_evals: torch.Tensor, exp: 
     if rc:
         raise RuntimeError(f"kzg open evals: launch failed ({rc})")
     return work
+
+
+GT_OUT_BYTES = 580  # 576 B of GT, then the u32 verdict
+
+
+def pairing_product_dev(d_g1: torch.Tensor, d_g2: torch.Tensor, d_out: torch.Tensor, key: torch.Tensor,
+                        work: torch.Tensor | None = None) -> torch.Tensor:
+    """Asynchronous product of pairings on device tensors (torch's current stream): k ark G1 records
+    and k ark G2 records in, 580 bytes (GT ‖ u32: 1 if the product is one) into d_out. Allocates the
+    workspace (kzgpot_pairing_workspace bytes) unless `work` is given; returns it — keep it alive until
+    the stream has run the call."""
+    k = d_g1.numel() // 96
+    if d_g1.numel() != 96 * k or d_g2.numel() != 192 * k or d_out.numel() < GT_OUT_BYTES:
+        raise ValueError(f"pairing product: bad buffer sizes {d_g1.numel()} / {d_g2.numel()} / {d_out.numel()}")
+    if not all(t.is_cuda for t in (d_g1, d_g2, d_out, key)):
+        raise ValueError("pairing_product_dev needs device tensors")
+    lib = _lib.load()
+    need = int(lib.kzgpot_pairing_workspace(k))
+    if need == 0:
+        raise ValueError(f"pairing product: k = {k} is not supported")
+    work = _work(need, work, d_out.device, "pairing product")
+    rc = lib.kzgpot_pairing_product_dev(d_g1.data_ptr() if k else None, d_g2.data_ptr() if k else None, k,
+                                        d_out.data_ptr(), work.data_ptr(), key.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"pairing product: launch failed ({rc})")
+    return work
+
+
+def kzg_batch_check_dev(d_vk: torch.Tensor, d_commitments: torch.Tensor, d_points: torch.Tensor, d_values: torch.Tensor,
+                        d_proofs_w: torch.Tensor, d_randomizers: torch.Tensor, d_out: torch.Tensor, key: torch.Tensor,
+                        d_random_vs: torch.Tensor | None = None, window: int = 0,
+                        work: torch.Tensor | None = None) -> torch.Tensor:
+    """Asynchronous KZG10 batch_check on device tensors (torch's current stream): the 576-byte packed
+    verifier key, n commitments and n proofs (ark G1 records), n points, values, randomizers (and
+    random_vs, None: none hiding) of 32 bytes each; 580 bytes (GT ‖ u32: 1 if accepted) into d_out.
+    Allocates the workspace (kzgpot_kzg_batch_check_workspace bytes) unless `work` is given; returns it
+    — keep it alive until the stream has run the call."""
+    n = d_commitments.numel() // 96
+    scalars = [d_points, d_values, d_randomizers] + ([d_random_vs] if d_random_vs is not None else [])
+    if (d_vk.numel() != 576 or d_commitments.numel() != 96 * n or d_proofs_w.numel() != 96 * n
+            or any(t.numel() != 32 * n for t in scalars) or d_out.numel() < GT_OUT_BYTES):
+        raise ValueError(f"kzg batch check: bad buffer sizes for n = {n}")
+    if not all(t.is_cuda for t in [d_vk, d_commitments, d_proofs_w, d_out, key] + scalars):
+        raise ValueError("kzg_batch_check_dev needs device tensors")
+    lib = _lib.load()
+    flags = window << 8
+    need = int(lib.kzgpot_kzg_batch_check_workspace(n, flags))
+    if need == 0:
+        raise ValueError(f"kzg batch check: n = {n} with window {window} is not supported")
+    work = _work(need, work, d_out.device, "kzg batch check")
+    ptr = lambda t: t.data_ptr() if t is not None and n else None  # noqa: E731
+    rc = lib.kzgpot_kzg_batch_check_dev(d_vk.data_ptr(), ptr(d_commitments), ptr(d_points), ptr(d_values), ptr(d_proofs_w),
+                                        ptr(d_random_vs), ptr(d_randomizers), n, d_out.data_ptr(), flags,
+                                        work.data_ptr(), key.data_ptr(), _stream())
+    if rc:
+        raise RuntimeError(f"kzg batch check: launch failed ({rc})")
+    return work

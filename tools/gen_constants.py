@@ -12,7 +12,9 @@ with R = 2^392. Everything here is derived from p, r and u (BLS12-381) and re-ch
     value < (c - 0.001) p;
   * the window schedule for a^((p-3)/4) (Fp square root and inverse square root): BLS12-381 over
     an 8-entry table chosen for its exponent, BN254 a w = 4 sliding window;
-  * 32-bit words of p for byte-level range checks; generator points (synthetic data).
+  * 32-bit words of p for byte-level range checks; generator points (synthetic data);
+  * FP12_FROB: the Frobenius factors of the pairing's final exponentiation
+    (tools/gen_pairing_constants.py derives them).
 """
 from __future__ import annotations
 
@@ -22,6 +24,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "oracle"))
 import kzgpot_oracle as O  # noqa: E402
+
+sys.path.insert(0, HERE)
+import gen_pairing_constants  # noqa: E402
 
 P, R, U = O.P, O.R_ORDER, O.U_PARAM
 LB = 28                 # limb bits
@@ -286,6 +291,7 @@ def main():
         "static constexpr int BLS_ABS_U_BITS = %d;" % absu.bit_length(),
         arr("FR_R", words32(R, 8), "group order r (ref-mode double-and-add)"),
         "static constexpr int FR_R_BITS = %d;" % R.bit_length(),
+    ] + gen_pairing_constants.header_lines(limbs28, mont) + [
         "}  // namespace kzgpot",
         "",
     ]
