@@ -1,5 +1,7 @@
-// Device-side helpers of the C ABI units (capi.hip, preprocess.hip, phase2.hip): HIP error
-// handling, the bad-key protocol of every launch, the current device and per-call device memory.
+// Device-side helpers of the C ABI units (capi.hip, preprocess.hip, phase2.hip, msm.hip, open.hip,
+// domain.hip, evals.hip, pairing.hip, verify.hip) and of the test hooks: HIP error handling, the
+// bad-key protocol of every launch, the current device, per-call device memory and the host-buffer
+// form of a `_dev` entry point (StagedCall).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -82,5 +84,70 @@ struct DevBuf {
     return 0;
   }
 };
+
+// The host-buffer form of a `_dev` entry point: the same call on the caller's host memory, synchronous,
+// on the null stream of the current device. Its contract, for every entry point that has one:
+//   - the function resets *first_bad and checks its arguments (KZGPOT_E_INVALID_ARG) before it declares a
+//     StagedCall, so an argument error uses no device;
+//   - begin() is the first step: KZGPOT_E_DEVICE without a device, before anything is allocated or written;
+//   - inputs go through per-call device buffers, all freed on every exit path; any HIP failure is
+//     KZGPOT_E_DEVICE;
+//   - finish() takes the `_dev` call's return value. A keyed call's key is read there: a rejection returns
+//     decode_key() and NOTHING is written to a caller buffer; otherwise `out` copies the results out;
+//   - the caller's current device is restored on return.
+// Every step but finish() returns 0 or KZGPOT_E_DEVICE, so the steps chain with ||.
+class StagedCall {
+ public:
+  uint64_t* d_key = nullptr;  // the key word of a keyed call, once key() has run
+
+  int begin() { return device_count() > 0 ? 0 : KZGPOT_E_DEVICE; }
+  // d = `bytes` of device memory (0: a valid 1-byte buffer)
+  template <class T>
+  int alloc(T*& d, size_t bytes) {
+    if (used_ == kMaxBufs || bufs_[used_].alloc(bytes)) return KZGPOT_E_DEVICE;
+    d = (T*)bufs_[used_++].p;
+    return 0;
+  }
+  // `bytes` of host memory to d, which may point into a buffer of alloc()'s (0: src is not read)
+  int copy_in(void* d, const void* src, size_t bytes) {
+    if (bytes) HIP_TRY(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+  }
+  template <class T>
+  int in(T*& d, const void* src, size_t bytes) {
+    return alloc(d, bytes) || copy_in(d, src, bytes) ? KZGPOT_E_DEVICE : 0;
+  }
+  int key() { return alloc(d_key, sizeof(uint64_t)); }
+  // rc: what the `_dev` call on the null stream returned; first_bad: null for a call without a key
+  template <class Out>
+  int finish(int rc, int64_t* first_bad, Out&& out) {
+    if (rc) return rc;
+    uint64_t k = kNoBad;
+    if (d_key)
+      HIP_TRY(hipMemcpy(&k, d_key, sizeof k, hipMemcpyDeviceToHost));
+    else
+      HIP_TRY(hipStreamSynchronize(nullptr));
+    if (k != kNoBad) return decode_key(k, first_bad);  // rejected: nothing is written
+    return out();
+  }
+
+ private:
+  static constexpr int kMaxBufs = 8;
+  DeviceGuard guard_;
+  DevBuf bufs_[kMaxBufs];
+  int used_ = 0;
+};
+
+inline int copy_out(void* dst, const void* d, size_t bytes) {
+  HIP_TRY(hipMemcpy(dst, d, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The verdict of a pairing product's or a check's d_out (GT bytes, then the u32): 1 or 0
+inline int read_verdict(const void* d_out) {
+  uint32_t v;
+  HIP_TRY(hipMemcpy(&v, (const uint8_t*)d_out + KZGPOT_GT_BYTES, sizeof v, hipMemcpyDeviceToHost));
+  return v ? 1 : 0;
+}
 
 }  // namespace kzgpot

@@ -39,48 +39,37 @@ int ntt_dev(const void* d_in, uint32_t exp, void* d_out, uint32_t flags, void* d
 int ntt_host(const uint8_t* in, uint32_t exp, uint8_t* out, uint32_t flags) {
   uint32_t t;
   if (!ntt_flags(flags, t) || exp > kNttMaxExp || !in || !out) return KZGPOT_E_INVALID_ARG;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
   const uint64_t bytes = (uint64_t)32 << exp;
-  DevBuf io, work;
-  if (io.alloc(bytes) || work.alloc(ntt_workspace_bytes(exp, t))) return KZGPOT_E_DEVICE;
-  HIP_TRY(hipMemcpy(io.p, in, bytes, hipMemcpyHostToDevice));
-  if (const int r = ntt_dev(io.p, exp, io.p, flags, work.p, nullptr)) return r;
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  HIP_TRY(hipMemcpy(out, io.p, bytes, hipMemcpyDeviceToHost));
-  return 0;
+  StagedCall call;
+  void *io, *work;
+  if (call.begin() || call.in(io, in, bytes) || call.alloc(work, ntt_workspace_bytes(exp, t))) return KZGPOT_E_DEVICE;
+  return call.finish(ntt_dev(io, exp, io, flags, work, nullptr), nullptr, [&] { return copy_out(out, io, bytes); });
 }
 
 // ---------------------------------------------------------------- the table
 bool table_args(uint32_t exp, const void* powers, const void* table) { return exp <= kOpenDomainMaxExp && powers && table; }
 
-int table_dev(bool g2, const void* d_powers, uint32_t exp, void* d_table, void* d_work, uint64_t* d_bad_key, void* stream,
-              uint64_t* host_key = nullptr) {
+int table_dev(bool g2, const void* d_powers, uint32_t exp, void* d_table, void* d_work, uint64_t* d_bad_key, void* stream) {
   if (!table_args(exp, d_powers, d_table) || !d_work || !d_bad_key) return KZGPOT_E_INVALID_ARG;
   FftScalars sc;
   fft_scalars(exp + 1, false, sc);
   const hipStream_t s = (hipStream_t)stream;
   return launch_with_key(d_bad_key, s, [&](unsigned long long* key) {
     return launch_open_domain_table(g2, d_powers, exp, d_table, sc, d_work, key, s);
-  }, host_key);
+  });
 }
 
 int table_host(bool g2, const uint8_t* powers, uint32_t exp, uint8_t* table, int64_t* first_bad) {
   if (first_bad) *first_bad = -1;
   if (!table_args(exp, powers, table)) return KZGPOT_E_INVALID_ARG;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
   const uint64_t in_bytes = point_record(g2) << exp;
-  DevBuf d_powers, d_table, work, key;
-  if (d_powers.alloc(in_bytes) || d_table.alloc(2 * in_bytes) || work.alloc(open_domain_table_workspace_bytes(g2, exp)) ||
-      key.alloc(sizeof(uint64_t)))
+  StagedCall call;
+  void *d_powers, *d_table, *work;
+  if (call.begin() || call.in(d_powers, powers, in_bytes) || call.alloc(d_table, 2 * in_bytes) ||
+      call.alloc(work, open_domain_table_workspace_bytes(g2, exp)) || call.key())
     return KZGPOT_E_DEVICE;
-  HIP_TRY(hipMemcpy(d_powers.p, powers, in_bytes, hipMemcpyHostToDevice));
-  uint64_t k;
-  if (const int r = table_dev(g2, d_powers.p, exp, d_table.p, work.p, (uint64_t*)key.p, nullptr, &k)) return r;
-  if (k != kNoBad) return decode_key(k, first_bad);  // rejected: nothing is written
-  HIP_TRY(hipMemcpy(table, d_table.p, 2 * in_bytes, hipMemcpyDeviceToHost));
-  return 0;
+  return call.finish(table_dev(g2, d_powers, exp, d_table, work, call.d_key, nullptr), first_bad,
+                     [&] { return copy_out(table, d_table, 2 * in_bytes); });
 }
 
 // ---------------------------------------------------------------- the openings
@@ -91,10 +80,9 @@ bool open_args(uint32_t flags, uint32_t exp, uint64_t n_coeffs, const void* tabl
          (!n_coeffs || coeffs);
 }
 
-// The steps are open_domain_plan's (plans.hpp); host_key (optional): receives the bad key once the
-// proofs are done
+// The steps are open_domain_plan's (plans.hpp)
 int open_dev(bool g2, const void* d_table, const void* d_coeffs, uint64_t nc, uint32_t exp, void* d_proofs,
-             void* d_values, uint32_t flags, void* d_work, uint64_t* d_bad_key, void* stream, uint64_t* host_key = nullptr) {
+             void* d_values, uint32_t flags, void* d_work, uint64_t* d_bad_key, void* stream) {
   uint32_t t;
   if (!open_args(flags, exp, nc, d_table, d_coeffs, d_proofs, t) || !d_work || !d_bad_key) return KZGPOT_E_INVALID_ARG;
   const OpenDomainPlan p = open_domain_plan(g2, exp, t);
@@ -126,7 +114,7 @@ int open_dev(bool g2, const void* d_table, const void* d_coeffs, uint64_t nc, ui
           e = launch_open_domain_step(g2, p, p.step[k], d_table, d_proofs, wide, out, d_work, key, s);
       }
     return e;
-  }, host_key);
+  });
 }
 
 int open_host(bool g2, const uint8_t* table, const uint8_t* coeffs, uint64_t nc, uint32_t exp, uint8_t* proofs,
@@ -134,24 +122,20 @@ int open_host(bool g2, const uint8_t* table, const uint8_t* coeffs, uint64_t nc,
   if (first_bad) *first_bad = -1;
   uint32_t t;
   if (!open_args(flags, exp, nc, table, coeffs, proofs, t)) return KZGPOT_E_INVALID_ARG;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
   const uint64_t n = (uint64_t)1 << exp, rec = point_record(g2);
-  DevBuf d_table, d_coeffs, d_proofs, d_values, work, key;
+  StagedCall call;
   // no coefficients, no values wanted: no buffer (open_dev takes a null pointer for either)
-  if (d_table.alloc(2 * n * rec) || (nc && d_coeffs.alloc(nc * 32)) || d_proofs.alloc(n * rec) ||
-      (values && d_values.alloc(n * 32)) || work.alloc(open_domain_plan(g2, exp, t).bytes) || key.alloc(sizeof(uint64_t)))
+  void *d_table, *d_coeffs = nullptr, *d_proofs, *d_values = nullptr, *work;
+  if (call.begin() || call.in(d_table, table, 2 * n * rec) || (nc && call.in(d_coeffs, coeffs, nc * 32)) ||
+      call.alloc(d_proofs, n * rec) || (values && call.alloc(d_values, n * 32)) ||
+      call.alloc(work, open_domain_plan(g2, exp, t).bytes) || call.key())
     return KZGPOT_E_DEVICE;
-  HIP_TRY(hipMemcpy(d_table.p, table, 2 * n * rec, hipMemcpyHostToDevice));
-  if (nc) HIP_TRY(hipMemcpy(d_coeffs.p, coeffs, nc * 32, hipMemcpyHostToDevice));
-  uint64_t k;
-  if (const int r = open_dev(g2, d_table.p, d_coeffs.p, nc, exp, d_proofs.p, values ? d_values.p : nullptr, flags, work.p,
-                             (uint64_t*)key.p, nullptr, &k))
-    return r;
-  if (k != kNoBad) return decode_key(k, first_bad);  // rejected: nothing is written
-  HIP_TRY(hipMemcpy(proofs, d_proofs.p, n * rec, hipMemcpyDeviceToHost));
-  if (values) HIP_TRY(hipMemcpy(values, d_values.p, n * 32, hipMemcpyDeviceToHost));
-  return 0;
+  const auto out = [&] {
+    if (const int r = copy_out(proofs, d_proofs, n * rec)) return r;
+    return values ? copy_out(values, d_values, n * 32) : 0;
+  };
+  return call.finish(open_dev(g2, d_table, d_coeffs, nc, exp, d_proofs, d_values, flags, work, call.d_key, nullptr),
+                     first_bad, out);
 }
 
 }  // namespace

@@ -29,15 +29,10 @@ int batch_inverse_host(const uint8_t* in, uint64_t n, uint8_t* out, uint32_t fla
   uint32_t t;
   if (!inverse_args(n, flags, in, out, t)) return KZGPOT_E_INVALID_ARG;
   if (!n) return 0;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
-  DevBuf io;
-  if (io.alloc(n * 32)) return KZGPOT_E_DEVICE;
-  HIP_TRY(hipMemcpy(io.p, in, n * 32, hipMemcpyHostToDevice));
-  if (const int r = batch_inverse_dev(io.p, n, io.p, flags, nullptr)) return r;
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  HIP_TRY(hipMemcpy(out, io.p, n * 32, hipMemcpyDeviceToHost));
-  return 0;
+  StagedCall call;
+  void* io;
+  if (call.begin() || call.in(io, in, n * 32)) return KZGPOT_E_DEVICE;
+  return call.finish(batch_inverse_dev(io, n, io, flags, nullptr), nullptr, [&] { return copy_out(out, io, n * 32); });
 }
 
 // ---------------------------------------------------------------- division in evaluation form
@@ -55,25 +50,22 @@ int evals_divide_host(const uint8_t* evals, uint32_t exp, const uint8_t* z, uint
                       uint32_t flags) {
   const uint64_t work_bytes = eval_workspace_bytes(exp, flags);
   if (!work_bytes || !evals || !z || !value) return KZGPOT_E_INVALID_ARG;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
   const uint64_t bytes = (uint64_t)32 << exp;
-  DevBuf d_evals, d_quot, d_value, work;
-  if (d_evals.alloc(bytes) || (quotient && d_quot.alloc(bytes)) || d_value.alloc(32) || work.alloc(work_bytes))
+  StagedCall call;
+  void *d_evals, *d_quot = nullptr, *d_value, *work;  // no quotient wanted: no buffer
+  if (call.begin() || call.in(d_evals, evals, bytes) || (quotient && call.alloc(d_quot, bytes)) ||
+      call.alloc(d_value, 32) || call.alloc(work, work_bytes))
     return KZGPOT_E_DEVICE;
-  HIP_TRY(hipMemcpy(d_evals.p, evals, bytes, hipMemcpyHostToDevice));
-  if (const int r = evals_divide_dev(d_evals.p, exp, z, d_quot.p, d_value.p, flags, work.p, nullptr)) return r;
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  HIP_TRY(hipMemcpy(value, d_value.p, 32, hipMemcpyDeviceToHost));
-  if (quotient) HIP_TRY(hipMemcpy(quotient, d_quot.p, bytes, hipMemcpyDeviceToHost));
-  return 0;
+  return call.finish(evals_divide_dev(d_evals, exp, z, d_quot, d_value, flags, work, nullptr), nullptr, [&] {
+    if (const int r = copy_out(value, d_value, 32)) return r;
+    return quotient ? copy_out(quotient, d_quot, bytes) : 0;
+  });
 }
 
 // ---------------------------------------------------------------- open
-// The workspace is open_evals_plan's (plans.hpp); host_key (optional): receives the bad key once the
-// proof is done
+// The workspace is open_evals_plan's (plans.hpp)
 int open_evals_dev(const void* d_lagrange, const void* d_evals, uint32_t exp, const uint8_t* z, void* d_out, uint32_t flags,
-                   void* d_work, uint64_t* d_bad_key, void* stream, uint64_t* host_key = nullptr) {
+                   void* d_work, uint64_t* d_bad_key, void* stream) {
   const OpenEvalsPlan p = open_evals_plan(exp, flags);
   if (!p.ok || !d_lagrange || !d_evals || !z || !d_out || !d_work || !d_bad_key) return KZGPOT_E_INVALID_ARG;
   fr_eval_scalars sc;
@@ -88,7 +80,7 @@ int open_evals_dev(const void* d_lagrange, const void* d_evals, uint32_t exp, co
                         p.c ? p.c : msm_window_bits(p.ev.n), w + p.msm, key, s)))
       return e;
     return launch_evals_emit(value, (uint8_t*)d_out + kPointBytes, key, s);
-  }, host_key);
+  });
 }
 
 int open_evals_host(const uint8_t* lagrange, const uint8_t* evals, uint32_t exp, const uint8_t* z, uint8_t* out,
@@ -96,20 +88,13 @@ int open_evals_host(const uint8_t* lagrange, const uint8_t* evals, uint32_t exp,
   if (first_bad) *first_bad = -1;
   const OpenEvalsPlan p = open_evals_plan(exp, flags);
   if (!p.ok || !lagrange || !evals || !z || !out) return KZGPOT_E_INVALID_ARG;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
-  DevBuf d_bases, d_evals, d_out, work, key;
-  if (d_bases.alloc(p.ev.n * p.rec) || d_evals.alloc(p.ev.n * 32) || d_out.alloc(kOutBytes) || work.alloc(p.bytes) ||
-      key.alloc(sizeof(uint64_t)))
+  StagedCall call;
+  void *d_bases, *d_evals, *d_out, *work;
+  if (call.begin() || call.in(d_bases, lagrange, p.ev.n * p.rec) || call.in(d_evals, evals, p.ev.n * 32) ||
+      call.alloc(d_out, kOutBytes) || call.alloc(work, p.bytes) || call.key())
     return KZGPOT_E_DEVICE;
-  HIP_TRY(hipMemcpy(d_bases.p, lagrange, p.ev.n * p.rec, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_evals.p, evals, p.ev.n * 32, hipMemcpyHostToDevice));
-  uint64_t k;
-  if (const int r = open_evals_dev(d_bases.p, d_evals.p, exp, z, d_out.p, flags, work.p, (uint64_t*)key.p, nullptr, &k))
-    return r;
-  if (k != kNoBad) return decode_key(k, first_bad);  // rejected: nothing is written
-  HIP_TRY(hipMemcpy(out, d_out.p, kOutBytes, hipMemcpyDeviceToHost));
-  return 0;
+  return call.finish(open_evals_dev(d_bases, d_evals, exp, z, d_out, flags, work, call.d_key, nullptr), first_bad,
+                     [&] { return copy_out(out, d_out, kOutBytes); });
 }
 
 }  // namespace

@@ -8,9 +8,8 @@ using namespace kzgpot;
 
 namespace {
 
-// host_key (optional): receives the bad key once the sum is done
 int msm_dev(bool g2, const void* d_bases, const void* d_scalars, uint64_t n, void* d_out, uint32_t flags, void* d_work,
-            uint64_t* d_bad_key, void* stream, uint64_t* host_key = nullptr) {
+            uint64_t* d_bad_key, void* stream) {
   uint32_t c;
   if (!msm_flags(flags, c) || !msm_workspace_bytes(g2, n, c) || !d_out || !d_work || !d_bad_key || (n && (!d_bases || !d_scalars)))
     return KZGPOT_E_INVALID_ARG;
@@ -18,7 +17,7 @@ int msm_dev(bool g2, const void* d_bases, const void* d_scalars, uint64_t n, voi
   return launch_with_key(d_bad_key, s, [&](unsigned long long* key) {
     return launch_msm(g2, d_bases, d_scalars, n, d_out, flags & KZGPOT_MSM_BASES_MONT, c ? c : msm_window_bits(n),
                       d_work, key, s);
-  }, host_key);
+  });
 }
 
 int msm_host(bool g2, const uint8_t* bases, const uint8_t* scalars, uint64_t n, uint8_t* out, uint32_t flags,
@@ -27,23 +26,14 @@ int msm_host(bool g2, const uint8_t* bases, const uint8_t* scalars, uint64_t n, 
   uint32_t c;
   const uint64_t work_bytes = msm_flags(flags, c) ? msm_workspace_bytes(g2, n, c) : 0;
   if (!work_bytes || !out || (n && (!bases || !scalars))) return KZGPOT_E_INVALID_ARG;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
   const uint64_t rec = base_record(g2, flags & KZGPOT_MSM_BASES_MONT), out_bytes = point_record(g2);
-  DevBuf d_bases, d_scalars, d_out, work, key;
-  if (d_bases.alloc(n * rec) || d_scalars.alloc(n * 32) || d_out.alloc(out_bytes) || work.alloc(work_bytes) ||
-      key.alloc(sizeof(uint64_t)))
+  StagedCall call;
+  void *d_bases, *d_scalars, *d_out, *work;
+  if (call.begin() || call.in(d_bases, bases, n * rec) || call.in(d_scalars, scalars, n * 32) ||
+      call.alloc(d_out, out_bytes) || call.alloc(work, work_bytes) || call.key())
     return KZGPOT_E_DEVICE;
-  if (n) {
-    HIP_TRY(hipMemcpy(d_bases.p, bases, n * rec, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_scalars.p, scalars, n * 32, hipMemcpyHostToDevice));
-  }
-  uint64_t k;
-  if (const int r = msm_dev(g2, d_bases.p, d_scalars.p, n, d_out.p, flags, work.p, (uint64_t*)key.p, nullptr, &k))
-    return r;
-  if (k != kNoBad) return decode_key(k, first_bad);  // rejected: nothing is written
-  HIP_TRY(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
-  return 0;
+  return call.finish(msm_dev(g2, d_bases, d_scalars, n, d_out, flags, work, call.d_key, nullptr), first_bad,
+                     [&] { return copy_out(out, d_out, out_bytes); });
 }
 
 }  // namespace

@@ -35,27 +35,23 @@ int poly_divide_host(const uint8_t* coeffs, uint64_t n, const uint8_t* z, uint8_
   uint32_t t;
   const uint64_t work_bytes = poly_flags(flags, t) ? poly_workspace_bytes(n, t) : 0;
   if (!work_bytes || !z || !value || (n && !coeffs)) return KZGPOT_E_INVALID_ARG;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
   const uint64_t nq = n ? n - 1 : 0;
-  DevBuf d_coeffs, d_quot, d_value, work;
-  if (d_coeffs.alloc(n * 32) || d_quot.alloc(nq * 32) || d_value.alloc(32) || work.alloc(work_bytes))
+  StagedCall call;
+  void *d_coeffs, *d_quot = nullptr, *d_value, *work;  // no quotient wanted: no buffer
+  if (call.begin() || call.in(d_coeffs, coeffs, n * 32) || (quotient && call.alloc(d_quot, nq * 32)) ||
+      call.alloc(d_value, 32) || call.alloc(work, work_bytes))
     return KZGPOT_E_DEVICE;
-  if (n) HIP_TRY(hipMemcpy(d_coeffs.p, coeffs, n * 32, hipMemcpyHostToDevice));
-  if (const int r = poly_divide_dev(d_coeffs.p, n, z, quotient ? d_quot.p : nullptr, d_value.p, flags, work.p, nullptr))
-    return r;
-  HIP_TRY(hipStreamSynchronize(nullptr));
-  HIP_TRY(hipMemcpy(value, d_value.p, 32, hipMemcpyDeviceToHost));
-  if (quotient && nq) HIP_TRY(hipMemcpy(quotient, d_quot.p, nq * 32, hipMemcpyDeviceToHost));
-  return 0;
+  return call.finish(poly_divide_dev(d_coeffs, n, z, d_quot, d_value, flags, work, nullptr), nullptr, [&] {
+    if (const int r = copy_out(value, d_value, 32)) return r;
+    return quotient && nq ? copy_out(quotient, d_quot, nq * 32) : 0;
+  });
 }
 
 // ---------------------------------------------------------------- open
 // The workspace is open_plan's (plans.hpp).
-// host_key (optional): receives the bad key once the proof is done
 int open_dev(const void* d_powers_of_g, const void* d_coeffs, uint64_t n, const void* d_powers_of_gamma_g,
              const void* d_blinding, uint64_t n_blind, const uint8_t* z, void* d_out, uint32_t flags, void* d_work,
-             uint64_t* d_bad_key, void* stream, uint64_t* host_key = nullptr) {
+             uint64_t* d_bad_key, void* stream) {
   const OpenPlan p = open_plan(n, n_blind, flags);
   if (!p.ok || !z || !d_out || !d_work || !d_bad_key || (n && !d_coeffs) || (n_blind && !d_blinding) ||
       (p.nq && !d_powers_of_g) || (p.nb && !d_powers_of_gamma_g))
@@ -78,7 +74,7 @@ int open_dev(const void* d_powers_of_g, const void* d_coeffs, uint64_t n, const 
                         p.c ? p.c : msm_window_bits(total), w + p.msm, key, s)))
       return e;
     return launch_open_emit(values, (uint8_t*)d_out + kPointBytes, key, s);
-  }, host_key);
+  });
 }
 
 int open_host(const uint8_t* powers_of_g, const uint8_t* coeffs, uint64_t n, const uint8_t* powers_of_gamma_g,
@@ -89,23 +85,14 @@ int open_host(const uint8_t* powers_of_g, const uint8_t* coeffs, uint64_t n, con
   if (!p.ok || !z || !out || (n && !coeffs) || (n_blind && !blinding) || (p.nq && !powers_of_g) ||
       (p.nb && !powers_of_gamma_g))
     return KZGPOT_E_INVALID_ARG;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
-  DevBuf d_pg, d_pgg, d_coeffs, d_blind, d_out, work, key;
-  if (d_pg.alloc(p.nq * p.rec) || d_pgg.alloc(p.nb * p.rec) || d_coeffs.alloc(n * 32) || d_blind.alloc(n_blind * 32) ||
-      d_out.alloc(kOutBytes) || work.alloc(p.bytes) || key.alloc(sizeof(uint64_t)))
+  StagedCall call;
+  void *d_pg, *d_pgg, *d_coeffs, *d_blind, *d_out, *work;
+  if (call.begin() || call.in(d_pg, powers_of_g, p.nq * p.rec) || call.in(d_pgg, powers_of_gamma_g, p.nb * p.rec) ||
+      call.in(d_coeffs, coeffs, n * 32) || call.in(d_blind, blinding, n_blind * 32) || call.alloc(d_out, kOutBytes) ||
+      call.alloc(work, p.bytes) || call.key())
     return KZGPOT_E_DEVICE;
-  if (p.nq) HIP_TRY(hipMemcpy(d_pg.p, powers_of_g, p.nq * p.rec, hipMemcpyHostToDevice));
-  if (p.nb) HIP_TRY(hipMemcpy(d_pgg.p, powers_of_gamma_g, p.nb * p.rec, hipMemcpyHostToDevice));
-  if (n) HIP_TRY(hipMemcpy(d_coeffs.p, coeffs, n * 32, hipMemcpyHostToDevice));
-  if (n_blind) HIP_TRY(hipMemcpy(d_blind.p, blinding, n_blind * 32, hipMemcpyHostToDevice));
-  uint64_t k;
-  if (const int r = open_dev(d_pg.p, d_coeffs.p, n, d_pgg.p, d_blind.p, n_blind, z, d_out.p, flags, work.p,
-                             (uint64_t*)key.p, nullptr, &k))
-    return r;
-  if (k != kNoBad) return decode_key(k, first_bad);  // rejected: nothing is written
-  HIP_TRY(hipMemcpy(out, d_out.p, kOutBytes, hipMemcpyDeviceToHost));
-  return 0;
+  return call.finish(open_dev(d_pg, d_coeffs, n, d_pgg, d_blind, n_blind, z, d_out, flags, work, call.d_key, nullptr),
+                     first_bad, [&] { return copy_out(out, d_out, kOutBytes); });
 }
 
 }  // namespace

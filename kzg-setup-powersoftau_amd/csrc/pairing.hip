@@ -1,7 +1,5 @@
 // C ABI (include/kzgpot.h): the product of pairings (kernels: pairing_kernels.hip; the workspace is
 // pairing_plan's, plans.hpp).
-#include <string.h>
-
 #include "codec.hpp"
 #include "device_rt.hpp"
 #include "host_rt.hpp"
@@ -12,39 +10,29 @@ namespace {
 
 constexpr uint64_t kOutBytes = KZGPOT_GT_BYTES + 4;  // GT, then the u32 "is one"
 
-// host_key (optional): receives the bad key once the product is done
 int pairing_dev(const void* d_g1, const void* d_g2, uint64_t k, void* d_out, void* d_work, uint64_t* d_bad_key,
-                void* stream, uint64_t* host_key = nullptr) {
+                void* stream) {
   if (!pairing_workspace_bytes(k) || !d_out || !d_work || !d_bad_key || (k && (!d_g1 || !d_g2))) return KZGPOT_E_INVALID_ARG;
   const hipStream_t s = (hipStream_t)stream;
   return launch_with_key(d_bad_key, s, [&](unsigned long long* key) {
     return launch_pairing_product(d_g1, d_g2, k, d_out, d_work, key, 0, s);
-  }, host_key);
+  });
 }
 
 int pairing_host(const uint8_t* g1, const uint8_t* g2, uint64_t k, uint8_t* out_gt, int64_t* first_bad) {
   if (first_bad) *first_bad = -1;
   const uint64_t work_bytes = pairing_workspace_bytes(k);
   if (!work_bytes || (k && (!g1 || !g2))) return KZGPOT_E_INVALID_ARG;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
-  DevBuf d_g1, d_g2, d_out, work, key;
-  if (d_g1.alloc(k * point_record(false)) || d_g2.alloc(k * point_record(true)) || d_out.alloc(kOutBytes) ||
-      work.alloc(work_bytes) || key.alloc(sizeof(uint64_t)))
+  StagedCall call;
+  void *d_g1, *d_g2, *d_out, *work;
+  if (call.begin() || call.in(d_g1, g1, k * point_record(false)) || call.in(d_g2, g2, k * point_record(true)) ||
+      call.alloc(d_out, kOutBytes) || call.alloc(work, work_bytes) || call.key())
     return KZGPOT_E_DEVICE;
-  if (k) {
-    HIP_TRY(hipMemcpy(d_g1.p, g1, k * point_record(false), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_g2.p, g2, k * point_record(true), hipMemcpyHostToDevice));
-  }
-  uint64_t bad;
-  if (const int r = pairing_dev(d_g1.p, d_g2.p, k, d_out.p, work.p, (uint64_t*)key.p, nullptr, &bad)) return r;
-  if (bad != kNoBad) return decode_key(bad, first_bad);  // rejected: nothing is written
-  uint8_t out[kOutBytes];
-  HIP_TRY(hipMemcpy(out, d_out.p, kOutBytes, hipMemcpyDeviceToHost));
-  if (out_gt) memcpy(out_gt, out, KZGPOT_GT_BYTES);
-  uint32_t is_one;
-  memcpy(&is_one, out + KZGPOT_GT_BYTES, 4);
-  return is_one ? 1 : 0;
+  return call.finish(pairing_dev(d_g1, d_g2, k, d_out, work, call.d_key, nullptr), first_bad, [&] {
+    const int is_one = read_verdict(d_out);  // before the GT bytes: an error here leaves out_gt alone
+    if (is_one >= 0 && out_gt && copy_out(out_gt, d_out, KZGPOT_GT_BYTES)) return KZGPOT_E_DEVICE;
+    return is_one;
+  });
 }
 
 }  // namespace

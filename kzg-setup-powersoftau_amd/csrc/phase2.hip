@@ -11,7 +11,7 @@ namespace {
 
 constexpr uint32_t kFftFlags = KZGPOT_FFT_INVERSE | KZGPOT_FFT_OUT_PAIRING;
 
-// host_key (optional): receives the bad key once the transform is done
+// host_key (optional, prepare_phase2_run's): receives the bad key once the transform is done
 int fft_dev(bool g2, const void* d_in, uint32_t exp, void* d_out, uint32_t flags, void* d_work, uint64_t* d_bad_key,
             void* stream, uint64_t* host_key = nullptr) {
   if (exp > 32 || !d_in || !d_out || !d_work || !d_bad_key || (flags & ~kFftFlags)) return KZGPOT_E_INVALID_ARG;
@@ -27,17 +27,13 @@ int fft_dev(bool g2, const void* d_in, uint32_t exp, void* d_out, uint32_t flags
 int fft_host(bool g2, const uint8_t* in, uint32_t exp, uint8_t* out, uint32_t flags, int64_t* first_bad) {
   if (first_bad) *first_bad = -1;
   if (exp > 32 || !in || !out || (flags & ~kFftFlags)) return KZGPOT_E_INVALID_ARG;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
   const uint64_t bytes = ((uint64_t)1 << exp) * (g2 ? 192 : 96);
-  DevBuf io, work, key;
-  if (io.alloc(bytes) || work.alloc(fft_workspace_bytes(g2, exp)) || key.alloc(sizeof(uint64_t))) return KZGPOT_E_DEVICE;
-  HIP_TRY(hipMemcpy(io.p, in, bytes, hipMemcpyHostToDevice));
-  uint64_t k;
-  if (const int r = fft_dev(g2, io.p, exp, io.p, flags, work.p, (uint64_t*)key.p, nullptr, &k)) return r;
-  if (k != kNoBad) return decode_key(k, first_bad);  // rejected: nothing is written
-  HIP_TRY(hipMemcpy(out, io.p, bytes, hipMemcpyDeviceToHost));
-  return 0;
+  StagedCall call;
+  void *io, *work;
+  if (call.begin() || call.in(io, in, bytes) || call.alloc(work, fft_workspace_bytes(g2, exp)) || call.key())
+    return KZGPOT_E_DEVICE;
+  return call.finish(fft_dev(g2, io, exp, io, flags, work, call.d_key, nullptr), first_bad,
+                     [&] { return copy_out(out, io, bytes); });
 }
 
 // a finite ark-uncompressed record -> pairing uncompressed (A6): every 48-B coordinate byte-reversed,

@@ -2,8 +2,6 @@
 // the negation by verify_kernels.hip, total_c and total_w by two launch_msm (msm_kernels.hip), the
 // product of the two pairings by launch_pairing_product (pairing_kernels.hip). The scalars, both sums
 // and both points never leave HBM. The workspace is check_plan's (plans.hpp).
-#include <string.h>
-
 #include "codec.hpp"
 #include "device_rt.hpp"
 #include "host_rt.hpp"
@@ -16,10 +14,9 @@ constexpr uint64_t kG1 = point_record(false), kG2 = point_record(true);
 constexpr uint64_t kVkBytes = 2 * kG1 + 2 * kG2, kOutBytes = KZGPOT_GT_BYTES + 4;
 static_assert(kVkBytes == 576, "g, gamma_g, h, beta_h");
 
-// host_key (optional): receives the bad key once the check is done
 int check_dev(const void* d_vk, const void* d_commitments, const void* d_points, const void* d_values,
               const void* d_proofs_w, const void* d_random_vs, const void* d_randomizers, uint64_t n, void* d_out,
-              uint32_t flags, void* d_work, uint64_t* d_bad_key, void* stream, uint64_t* host_key = nullptr) {
+              uint32_t flags, void* d_work, uint64_t* d_bad_key, void* stream) {
   const CheckPlan p = check_plan(n, flags);
   if (!p.ok || !d_vk || !d_out || !d_work || !d_bad_key ||
       (n && (!d_commitments || !d_points || !d_values || !d_proofs_w || !d_randomizers)))
@@ -48,7 +45,7 @@ int check_dev(const void* d_vk, const void* d_commitments, const void* d_points,
     if ((e = launch_g1_negate(total_w, s))) return e;
     // e(total_c, h) e(-total_w, beta_h); h and beta_h are records 2 n + 2 and 2 n + 3 of the call
     return launch_pairing_product(total_c, w + p.pairs_g2, 2, d_out, w + p.pairing, key, 2 * n, s);
-  }, host_key);
+  });
 }
 
 int check_host(const uint8_t* vk, const uint8_t* commitments, const uint8_t* points, const uint8_t* values,
@@ -57,32 +54,19 @@ int check_host(const uint8_t* vk, const uint8_t* commitments, const uint8_t* poi
   if (first_bad) *first_bad = -1;
   const CheckPlan p = check_plan(n, flags);
   if (!p.ok || !vk || (n && (!commitments || !points || !values || !proofs_w || !randomizers))) return KZGPOT_E_INVALID_ARG;
-  if (device_count() <= 0) return KZGPOT_E_DEVICE;
-  DeviceGuard guard;
-  DevBuf d_vk, d_points, d_scalars, d_out, work, key;
+  StagedCall call;
   // the G1 records end to end (commitments, proofs), the four scalar arrays end to end
-  const uint64_t ns = random_vs ? 4 : 3;
-  if (d_vk.alloc(kVkBytes) || d_points.alloc(2 * n * kG1) || d_scalars.alloc(ns * n * 32) || d_out.alloc(kOutBytes) ||
-      work.alloc(p.bytes) || key.alloc(sizeof(uint64_t)))
+  const uint64_t ns = random_vs ? 4 : 3, g = n * kG1, s = n * 32;
+  void *d_vk, *d_out, *work;
+  uint8_t *dp, *ds;
+  if (call.begin() || call.in(d_vk, vk, kVkBytes) || call.alloc(dp, 2 * g) || call.alloc(ds, ns * s) ||
+      call.alloc(d_out, kOutBytes) || call.alloc(work, p.bytes) || call.key() || call.copy_in(dp, commitments, g) ||
+      call.copy_in(dp + g, proofs_w, g) || call.copy_in(ds, points, s) || call.copy_in(ds + s, values, s) ||
+      call.copy_in(ds + 2 * s, randomizers, s) || (random_vs && call.copy_in(ds + 3 * s, random_vs, s)))
     return KZGPOT_E_DEVICE;
-  uint8_t *dp = (uint8_t*)d_points.p, *ds = (uint8_t*)d_scalars.p;
-  HIP_TRY(hipMemcpy(d_vk.p, vk, kVkBytes, hipMemcpyHostToDevice));
-  if (n) {
-    HIP_TRY(hipMemcpy(dp, commitments, n * kG1, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dp + n * kG1, proofs_w, n * kG1, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ds, points, n * 32, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ds + n * 32, values, n * 32, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ds + 2 * n * 32, randomizers, n * 32, hipMemcpyHostToDevice));
-    if (random_vs) HIP_TRY(hipMemcpy(ds + 3 * n * 32, random_vs, n * 32, hipMemcpyHostToDevice));
-  }
-  uint64_t bad;
-  if (const int r = check_dev(d_vk.p, dp, ds, ds + n * 32, dp + n * kG1, random_vs ? ds + 3 * n * 32 : nullptr,
-                              ds + 2 * n * 32, n, d_out.p, flags, work.p, (uint64_t*)key.p, nullptr, &bad))
-    return r;
-  if (bad != kNoBad) return decode_key(bad, first_bad);
-  uint32_t accepted;
-  HIP_TRY(hipMemcpy(&accepted, (uint8_t*)d_out.p + KZGPOT_GT_BYTES, 4, hipMemcpyDeviceToHost));
-  return accepted ? 1 : 0;
+  return call.finish(check_dev(d_vk, dp, ds, ds + s, dp + g, random_vs ? ds + 3 * s : nullptr, ds + 2 * s, n, d_out,
+                               flags, work, call.d_key, nullptr),
+                     first_bad, [&] { return read_verdict(d_out); });
 }
 
 }  // namespace

@@ -81,6 +81,14 @@ class CodecResult:
     status: bytes | None
 
 
+def _result(ret: int, fb, out: bytes, ok: bool | None = None) -> CodecResult:
+    """Of a staged call: an API or runtime error raises; `out` is empty unless the call succeeded
+    (ret == 0, or `ok` where success is another value)."""
+    if ret <= -100:
+        raise KzgPotError(ret)
+    return CodecResult(out if (ret == 0 if ok is None else ok) else b"", ret, fb.value, None)
+
+
 def _buf(data) -> tuple[ctypes.c_void_p, int, object]:
     if isinstance(data, (bytes, bytearray, memoryview)):
         b = bytes(data)
@@ -442,9 +450,7 @@ def _group_fft(g2: bool, data, exp: int, inverse: bool, pairing_out: bool) -> Co
     fn = _lib.load().kzgpot_g2_fft if g2 else _lib.load().kzgpot_g1_fft
     ret = fn(ptr, exp, out, flags, ctypes.byref(fb))
     del keep
-    if ret <= -100:
-        raise KzgPotError(ret)
-    return CodecResult(out.raw if ret == 0 else b"", ret, fb.value, None)
+    return _result(ret, fb, out.raw)
 
 
 def g1_fft(data, exp: int, inverse: bool = True, pairing_out: bool = False) -> CodecResult:
@@ -521,9 +527,7 @@ def _msm(g2: bool, bases, scalars, mont: bool, window: int) -> CodecResult:
     fn = _lib.load().kzgpot_g2_msm if g2 else _lib.load().kzgpot_g1_msm
     ret = fn(ptr, sc, nbytes // rec, out, msm_flags(mont, window), ctypes.byref(fb))
     del keep
-    if ret <= -100:
-        raise KzgPotError(ret)
-    return CodecResult(out.raw if ret == 0 else b"", ret, fb.value, None)
+    return _result(ret, fb, out.raw)
 
 
 def g1_msm(bases, scalars, mont: bool = False, window: int = 0) -> CodecResult:
@@ -630,9 +634,7 @@ def g1_kzg_open(powers_of_g, coeffs, powers_of_gamma_g, blinding, z, mont: bool 
     ret = _lib.load().kzgpot_g1_kzg_open(pg_ptr, p, n, pgg_ptr, q, nb, _fr_bytes(z), out,
                                          msm_flags(mont, window) | poly_flags(tile), ctypes.byref(fb))
     del keep1, keep2
-    if ret <= -100:
-        raise KzgPotError(ret)
-    return CodecResult(out.raw if ret == 0 else b"", ret, fb.value, None)
+    return _result(ret, fb, out.raw)
 
 
 def kzg_open(powers, coeffs, z, blinding=None, window: int = 0, tile: int = 0) -> KzgProof:
@@ -709,9 +711,7 @@ def _open_domain_table(g2: bool, records, exp: int) -> CodecResult:
     fn = _lib.load().kzgpot_g2_open_domain_table if g2 else _lib.load().kzgpot_g1_open_domain_table
     ret = fn(ptr, exp, out, ctypes.byref(fb))
     del keep
-    if ret <= -100:
-        raise KzgPotError(ret)
-    return CodecResult(out.raw if ret == 0 else b"", ret, fb.value, None)
+    return _result(ret, fb, out.raw)
 
 
 def open_domain_table(records, exp: int, g2: bool = False) -> bytes:
@@ -736,9 +736,7 @@ def _open_domain(g2: bool, table, coeffs, exp: int, tile: int, want_values: bool
     fn = _lib.load().kzgpot_g2_open_domain if g2 else _lib.load().kzgpot_g1_open_domain
     ret = fn(ptr, sc, len(sc) // 32, exp, proofs, values, ntt_flags(False, tile), ctypes.byref(fb))
     del keep
-    if ret <= -100:
-        raise KzgPotError(ret)
-    return CodecResult((proofs.raw + (values.raw if want_values else b"")) if ret == 0 else b"", ret, fb.value, None)
+    return _result(ret, fb, proofs.raw + (values.raw if want_values else b""))
 
 
 def g1_open_domain(table, coeffs, exp: int, tile: int = 0, want_values: bool = True) -> CodecResult:
@@ -858,9 +856,7 @@ def g1_kzg_open_evals(lagrange, evals, exp: int, z, mont: bool = False, window: 
     ret = _lib.load().kzgpot_g1_kzg_open_evals(ptr, data, exp, _fr_bytes(z), out,
                                                msm_flags(mont, window) | poly_flags(tile), ctypes.byref(fb))
     del keep
-    if ret <= -100:
-        raise KzgPotError(ret)
-    return CodecResult(out.raw if ret == 0 else b"", ret, fb.value, None)
+    return _result(ret, fb, out.raw)
 
 
 def kzg_open_evals(lagrange, evals, exp: int, z, window: int = 0, tile: int = 0) -> KzgProof:
@@ -901,9 +897,7 @@ def g1g2_pairing_product(g1_records, g2_records) -> CodecResult:
     fb = ctypes.c_int64(-1)
     ret = _lib.load().kzgpot_pairing_product(p1 if k else None, p2 if k else None, k, out, ctypes.byref(fb))
     del keep1, keep2
-    if ret <= -100:
-        raise KzgPotError(ret)
-    return CodecResult(out.raw if ret >= 0 else b"", ret, fb.value, None)
+    return _result(ret, fb, out.raw, ok=ret >= 0)
 
 
 def pairing_product(g1_records, g2_records):
@@ -945,9 +939,7 @@ def g1_kzg_batch_check(vk, commitments, points, values, proofs_w, random_vs, ran
     arg = lambda b: b if n else None  # noqa: E731
     ret = _lib.load().kzgpot_kzg_batch_check(_vk_bytes(vk), arg(c), arg(z), arg(v), arg(w), arg(rv) if rv is not None else None,
                                              arg(rho), n, msm_flags(False, window), ctypes.byref(fb))
-    if ret <= -100:
-        raise KzgPotError(ret)
-    return CodecResult(b"", ret, fb.value, None)
+    return _result(ret, fb, b"")
 
 
 def _proof_parts(proof):

@@ -106,6 +106,31 @@ def read_key(key: torch.Tensor) -> int:
     return int(key.item()) & ((1 << 64) - 1)
 
 
+def _work(need: int, work: torch.Tensor | None, device, what: str) -> torch.Tensor:
+    if work is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    if work.numel() < need:
+        raise ValueError(f"{what}: workspace of {work.numel()} B, {need} needed")
+    return work
+
+
+def _dev_call(what: str, tensors, need, work: torch.Tensor | None, unsupported: str, call) -> torch.Tensor | None:
+    """What every wrapper below does after its own size check: the tensors (None entries skipped) must
+    be on the device; `need` is the library's workspace size in bytes (None: the call takes no
+    workspace), 0 meaning the arguments named by `unsupported` are invalid; `work` is checked against
+    it, or allocated beside tensors[0]; `call(work)` makes the C call. Returns the workspace."""
+    if not all(t.is_cuda for t in tensors if t is not None):
+        raise ValueError(f"{what}: needs device tensors")
+    if need is not None:
+        if need == 0:
+            raise ValueError(f"{what}: {unsupported} is not supported")
+        work = _work(need, work, tensors[0].device, what)
+    rc = call(work)
+    if rc:
+        raise RuntimeError(f"{what}: launch failed ({rc})")
+    return work
+
+
 def group_fft_dev(g2: bool, d_in: torch.Tensor, exp: int, d_out: torch.Tensor, key: torch.Tensor,
                   inverse: bool = True, pairing_out: bool = False, work: torch.Tensor | None = None) -> torch.Tensor:
     """Asynchronous group FFT of 2^exp ark records on device tensors (torch's current stream);
@@ -114,20 +139,11 @@ def group_fft_dev(g2: bool, d_in: torch.Tensor, exp: int, d_out: torch.Tensor, k
     rec = 192 if g2 else 96
     if d_in.numel() != rec << exp or d_out.numel() < rec << exp:
         raise ValueError(f"group fft: bad buffer sizes {d_in.numel()} / {d_out.numel()}")
-    if not (d_in.is_cuda and d_out.is_cuda and key.is_cuda):
-        raise ValueError("group_fft_dev needs device tensors")
     lib = _lib.load()
-    need = int(lib.kzgpot_group_fft_workspace(int(g2), exp))
-    if work is None:
-        work = torch.empty(need, dtype=torch.uint8, device=d_in.device)
-    elif work.numel() < need:
-        raise ValueError(f"group fft: workspace of {work.numel()} B, {need} needed")
     flags = (1 if inverse else 0) | (2 if pairing_out else 0)
     fn = lib.kzgpot_g2_fft_dev if g2 else lib.kzgpot_g1_fft_dev
-    rc = fn(d_in.data_ptr(), exp, d_out.data_ptr(), flags, work.data_ptr(), key.data_ptr(), _stream())
-    if rc:
-        raise RuntimeError(f"group fft: launch failed ({rc})")
-    return work
+    return _dev_call("group fft", (d_in, d_out, key), int(lib.kzgpot_group_fft_workspace(int(g2), exp)), work, f"exp = {exp}",
+                     lambda w: fn(d_in.data_ptr(), exp, d_out.data_ptr(), flags, w.data_ptr(), key.data_ptr(), _stream()))
 
 
 def g1_fft_dev(d_in, exp, d_out, key, **kw) -> torch.Tensor:
@@ -148,23 +164,13 @@ def msm_dev(g2: bool, d_bases: torch.Tensor, d_scalars: torch.Tensor, d_out: tor
     n = d_scalars.numel() // 32
     if d_scalars.numel() != 32 * n or d_bases.numel() != rec * n or d_out.numel() < (192 if g2 else 96):
         raise ValueError(f"msm: bad buffer sizes {d_bases.numel()} / {d_scalars.numel()} / {d_out.numel()}")
-    if not (d_bases.is_cuda and d_scalars.is_cuda and d_out.is_cuda and key.is_cuda):
-        raise ValueError("msm_dev needs device tensors")
     lib = _lib.load()
     flags = (1 if mont else 0) | (window << 8)
-    need = int(lib.kzgpot_msm_workspace(int(g2), n, flags))
-    if need == 0:
-        raise ValueError(f"msm: n = {n} with window {window} is not supported")
-    if work is None:
-        work = torch.empty(need, dtype=torch.uint8, device=d_out.device)
-    elif work.numel() < need:
-        raise ValueError(f"msm: workspace of {work.numel()} B, {need} needed")
     fn = lib.kzgpot_g2_msm_dev if g2 else lib.kzgpot_g1_msm_dev
-    rc = fn(d_bases.data_ptr(), d_scalars.data_ptr(), n, d_out.data_ptr(), flags, work.data_ptr(), key.data_ptr(),
-            _stream())
-    if rc:
-        raise RuntimeError(f"msm: launch failed ({rc})")
-    return work
+    return _dev_call("msm", (d_out, d_bases, d_scalars, key), int(lib.kzgpot_msm_workspace(int(g2), n, flags)), work,
+                     f"n = {n} with window {window}",
+                     lambda w: fn(d_bases.data_ptr(), d_scalars.data_ptr(), n, d_out.data_ptr(), flags, w.data_ptr(),
+                                  key.data_ptr(), _stream()))
 
 
 def g1_msm_dev(d_bases, d_scalars, d_out, key, **kw) -> torch.Tensor:
@@ -173,14 +179,6 @@ def g1_msm_dev(d_bases, d_scalars, d_out, key, **kw) -> torch.Tensor:
 
 def g2_msm_dev(d_bases, d_scalars, d_out, key, **kw) -> torch.Tensor:
     return msm_dev(True, d_bases, d_scalars, d_out, key, **kw)
-
-
-def _work(need: int, work: torch.Tensor | None, device, what: str) -> torch.Tensor:
-    if work is None:
-        return torch.empty(need, dtype=torch.uint8, device=device)
-    if work.numel() < need:
-        raise ValueError(f"{what}: workspace of {work.numel()} B, {need} needed")
-    return work
 
 
 def fr_poly_divide_dev(d_coeffs: torch.Tensor, z: int, d_quotient: torch.Tensor | None, d_value: torch.Tensor,
@@ -192,20 +190,14 @@ def fr_poly_divide_dev(d_coeffs: torch.Tensor, z: int, d_quotient: torch.Tensor 
     n = d_coeffs.numel() // 32
     if d_coeffs.numel() != 32 * n or d_value.numel() < 32 or (d_quotient is not None and d_quotient.numel() < 32 * (n - 1)):
         raise ValueError(f"poly divide: bad buffer sizes {d_coeffs.numel()} / {d_value.numel()}")
-    if not (d_coeffs.is_cuda and d_value.is_cuda and (d_quotient is None or d_quotient.is_cuda)):
-        raise ValueError("fr_poly_divide_dev needs device tensors")
     lib = _lib.load()
     flags = tile << 16
-    need = int(lib.kzgpot_fr_poly_workspace(n, flags))
-    if need == 0:
-        raise ValueError(f"poly divide: n = {n} with tile {tile} is not supported")
-    work = _work(need, work, d_value.device, "poly divide")
-    rc = lib.kzgpot_fr_poly_divide_dev(d_coeffs.data_ptr(), n, int(z).to_bytes(32, "little"),
-                                       d_quotient.data_ptr() if d_quotient is not None else None, d_value.data_ptr(),
-                                       flags, work.data_ptr(), _stream())
-    if rc:
-        raise RuntimeError(f"poly divide: launch failed ({rc})")
-    return work
+    return _dev_call("poly divide", (d_value, d_coeffs, d_quotient), int(lib.kzgpot_fr_poly_workspace(n, flags)), work,
+                     f"n = {n} with tile {tile}",
+                     lambda w: lib.kzgpot_fr_poly_divide_dev(
+                         d_coeffs.data_ptr(), n, int(z).to_bytes(32, "little"),
+                         d_quotient.data_ptr() if d_quotient is not None else None, d_value.data_ptr(), flags, w.data_ptr(),
+                         _stream()))
 
 
 def g1_kzg_open_dev(d_powers_of_g: torch.Tensor, d_coeffs: torch.Tensor, z: int, d_out: torch.Tensor, key: torch.Tensor,
@@ -222,22 +214,16 @@ def g1_kzg_open_dev(d_powers_of_g: torch.Tensor, d_coeffs: torch.Tensor, z: int,
     if (d_coeffs.numel() != 32 * n or (nb and d_blinding.numel() != 32 * nb) or d_out.numel() < 160
             or d_powers_of_g.numel() < rec * max(0, n - 1) or pgg < rec * max(0, nb - 1)):
         raise ValueError(f"kzg open: bad buffer sizes {d_powers_of_g.numel()} / {d_coeffs.numel()} / {pgg} / {d_out.numel()}")
-    tensors = [d_powers_of_g, d_coeffs, d_out, key] + [t for t in (d_powers_of_gamma_g, d_blinding) if t is not None]
-    if not all(t.is_cuda for t in tensors):
-        raise ValueError("g1_kzg_open_dev needs device tensors")
     lib = _lib.load()
     flags = (1 if mont else 0) | (window << 8) | (tile << 16)
-    need = int(lib.kzgpot_kzg_open_workspace(n, nb, flags))
-    if need == 0:
-        raise ValueError(f"kzg open: n = {n}, n_blind = {nb} with window {window}, tile {tile} is not supported")
-    work = _work(need, work, d_out.device, "kzg open")
-    rc = lib.kzgpot_g1_kzg_open_dev(d_powers_of_g.data_ptr(), d_coeffs.data_ptr(), n,
-                                    d_powers_of_gamma_g.data_ptr() if d_powers_of_gamma_g is not None else None,
-                                    d_blinding.data_ptr() if nb else None, nb, int(z).to_bytes(32, "little"),
-                                    d_out.data_ptr(), flags, work.data_ptr(), key.data_ptr(), _stream())
-    if rc:
-        raise RuntimeError(f"kzg open: launch failed ({rc})")
-    return work
+    return _dev_call("kzg open", (d_out, d_powers_of_g, d_coeffs, key, d_powers_of_gamma_g, d_blinding),
+                     int(lib.kzgpot_kzg_open_workspace(n, nb, flags)), work,
+                     f"n = {n}, n_blind = {nb} with window {window}, tile {tile}",
+                     lambda w: lib.kzgpot_g1_kzg_open_dev(
+                         d_powers_of_g.data_ptr(), d_coeffs.data_ptr(), n,
+                         d_powers_of_gamma_g.data_ptr() if d_powers_of_gamma_g is not None else None,
+                         d_blinding.data_ptr() if nb else None, nb, int(z).to_bytes(32, "little"), d_out.data_ptr(), flags,
+                         w.data_ptr(), key.data_ptr(), _stream()))
 
 
 def fr_ntt_dev(d_in: torch.Tensor, exp: int, d_out: torch.Tensor, inverse: bool = False, tile: int = 0,
@@ -248,18 +234,10 @@ def fr_ntt_dev(d_in: torch.Tensor, exp: int, d_out: torch.Tensor, inverse: bool 
     until the stream has run the call."""
     if d_in.numel() != 32 << exp or d_out.numel() < 32 << exp:
         raise ValueError(f"ntt: bad buffer sizes {d_in.numel()} / {d_out.numel()}")
-    if not (d_in.is_cuda and d_out.is_cuda):
-        raise ValueError("fr_ntt_dev needs device tensors")
     lib = _lib.load()
     flags = (1 if inverse else 0) | (tile << 16)
-    need = int(lib.kzgpot_fr_ntt_workspace(exp, flags))
-    if need == 0:
-        raise ValueError(f"ntt: exp = {exp} with tile {tile} is not supported")
-    work = _work(need, work, d_out.device, "ntt")
-    rc = lib.kzgpot_fr_ntt_dev(d_in.data_ptr(), exp, d_out.data_ptr(), flags, work.data_ptr(), _stream())
-    if rc:
-        raise RuntimeError(f"ntt: launch failed ({rc})")
-    return work
+    return _dev_call("ntt", (d_out, d_in), int(lib.kzgpot_fr_ntt_workspace(exp, flags)), work, f"exp = {exp} with tile {tile}",
+                     lambda w: lib.kzgpot_fr_ntt_dev(d_in.data_ptr(), exp, d_out.data_ptr(), flags, w.data_ptr(), _stream()))
 
 
 def open_domain_table_dev(g2: bool, d_powers: torch.Tensor, exp: int, d_table: torch.Tensor, key: torch.Tensor,
@@ -269,18 +247,11 @@ def open_domain_table_dev(g2: bool, d_powers: torch.Tensor, exp: int, d_table: t
     rec = 192 if g2 else 96
     if d_powers.numel() < rec << exp or d_table.numel() < 2 * rec << exp:
         raise ValueError(f"open domain table: bad buffer sizes {d_powers.numel()} / {d_table.numel()}")
-    if not (d_powers.is_cuda and d_table.is_cuda and key.is_cuda):
-        raise ValueError("open_domain_table_dev needs device tensors")
     lib = _lib.load()
-    need = int(lib.kzgpot_open_domain_table_workspace(int(g2), exp))
-    if need == 0:
-        raise ValueError(f"open domain table: exp = {exp} is not supported")
-    work = _work(need, work, d_table.device, "open domain table")
     fn = lib.kzgpot_g2_open_domain_table_dev if g2 else lib.kzgpot_g1_open_domain_table_dev
-    rc = fn(d_powers.data_ptr(), exp, d_table.data_ptr(), work.data_ptr(), key.data_ptr(), _stream())
-    if rc:
-        raise RuntimeError(f"open domain table: launch failed ({rc})")
-    return work
+    return _dev_call("open domain table", (d_table, d_powers, key), int(lib.kzgpot_open_domain_table_workspace(int(g2), exp)),
+                     work, f"exp = {exp}",
+                     lambda w: fn(d_powers.data_ptr(), exp, d_table.data_ptr(), w.data_ptr(), key.data_ptr(), _stream()))
 
 
 def open_domain_dev(g2: bool, d_table: torch.Tensor, d_coeffs: torch.Tensor, exp: int, d_proofs: torch.Tensor,
@@ -296,21 +267,16 @@ def open_domain_dev(g2: bool, d_table: torch.Tensor, d_coeffs: torch.Tensor, exp
     if (d_table.numel() != 2 * n * rec or d_coeffs.numel() != 32 * nc or d_proofs.numel() < n * rec
             or (d_values is not None and d_values.numel() < 32 * n)):
         raise ValueError(f"open domain: bad buffer sizes {d_table.numel()} / {d_coeffs.numel()} / {d_proofs.numel()}")
-    tensors = [d_table, d_coeffs, d_proofs, key] + ([d_values] if d_values is not None else [])
-    if not all(t.is_cuda for t in tensors):
-        raise ValueError("open_domain_dev needs device tensors")
     lib = _lib.load()
     flags = tile << 16
-    need = int(lib.kzgpot_open_domain_workspace(int(g2), exp, flags))
-    if need == 0 or nc > n:
-        raise ValueError(f"open domain: exp = {exp}, {nc} coefficients with tile {tile} is not supported")
-    work = _work(need, work, d_proofs.device, "open domain")
+    # more coefficients than points: not supported, as a tile the library does not take
+    need = 0 if nc > n else int(lib.kzgpot_open_domain_workspace(int(g2), exp, flags))
     fn = lib.kzgpot_g2_open_domain_dev if g2 else lib.kzgpot_g1_open_domain_dev
-    rc = fn(d_table.data_ptr(), d_coeffs.data_ptr() if nc else None, nc, exp, d_proofs.data_ptr(),
-            d_values.data_ptr() if d_values is not None else None, flags, work.data_ptr(), key.data_ptr(), _stream())
-    if rc:
-        raise RuntimeError(f"open domain: launch failed ({rc})")
-    return work
+    return _dev_call("open domain", (d_proofs, d_table, d_coeffs, key, d_values), need, work,
+                     f"exp = {exp}, {nc} coefficients with tile {tile}",
+                     lambda w: fn(d_table.data_ptr(), d_coeffs.data_ptr() if nc else None, nc, exp, d_proofs.data_ptr(),
+                                  d_values.data_ptr() if d_values is not None else None, flags, w.data_ptr(), key.data_ptr(),
+                                  _stream()))
 
 
 def g1_open_domain_dev(d_table, d_coeffs, exp, d_proofs, d_values, key, **kw) -> torch.Tensor:
@@ -327,12 +293,9 @@ def fr_batch_inverse_dev(d_in: torch.Tensor, d_out: torch.Tensor, tile: int = 0)
     n = d_in.numel() // 32
     if d_in.numel() != 32 * n or d_out.numel() < 32 * n:
         raise ValueError(f"batch inverse: bad buffer sizes {d_in.numel()} / {d_out.numel()}")
-    if not (d_in.is_cuda and d_out.is_cuda):
-        raise ValueError("fr_batch_inverse_dev needs device tensors")
-    rc = _lib.load().kzgpot_fr_batch_inverse_dev(d_in.data_ptr() if n else None, n, d_out.data_ptr() if n else None,
-                                                 tile << 16, _stream())
-    if rc:
-        raise RuntimeError(f"batch inverse: launch failed ({rc})")
+    _dev_call("batch inverse", (d_in, d_out), None, None, "",
+              lambda _: _lib.load().kzgpot_fr_batch_inverse_dev(d_in.data_ptr() if n else None, n,
+                                                                d_out.data_ptr() if n else None, tile << 16, _stream()))
 
 
 def fr_evals_divide_dev(d_evals: torch.Tensor, exp: int, z: int, d_quotient: torch.Tensor | None, d_value: torch.Tensor,
@@ -344,20 +307,14 @@ def fr_evals_divide_dev(d_evals: torch.Tensor, exp: int, z: int, d_quotient: tor
     if (d_evals.numel() != 32 << exp or d_value.numel() < 32
             or (d_quotient is not None and d_quotient.numel() < 32 << exp)):
         raise ValueError(f"evals divide: bad buffer sizes {d_evals.numel()} / {d_value.numel()}")
-    if not (d_evals.is_cuda and d_value.is_cuda and (d_quotient is None or d_quotient.is_cuda)):
-        raise ValueError("fr_evals_divide_dev needs device tensors")
     lib = _lib.load()
     flags = tile << 16
-    need = int(lib.kzgpot_fr_evals_workspace(exp, flags))
-    if need == 0:
-        raise ValueError(f"evals divide: exp = {exp} with tile {tile} is not supported")
-    work = _work(need, work, d_value.device, "evals divide")
-    rc = lib.kzgpot_fr_evals_divide_dev(d_evals.data_ptr(), exp, int(z).to_bytes(32, "little"),
-                                        d_quotient.data_ptr() if d_quotient is not None else None, d_value.data_ptr(),
-                                        flags, work.data_ptr(), _stream())
-    if rc:
-        raise RuntimeError(f"evals divide: launch failed ({rc})")
-    return work
+    return _dev_call("evals divide", (d_value, d_evals, d_quotient), int(lib.kzgpot_fr_evals_workspace(exp, flags)), work,
+                     f"exp = {exp} with tile {tile}",
+                     lambda w: lib.kzgpot_fr_evals_divide_dev(
+                         d_evals.data_ptr(), exp, int(z).to_bytes(32, "little"),
+                         d_quotient.data_ptr() if d_quotient is not None else None, d_value.data_ptr(), flags, w.data_ptr(),
+                         _stream()))
 
 
 def g1_kzg_open_evals_dev(d_lagrange: torch.Tensor, d_evals: torch.Tensor, exp: int, z: int, d_out: torch.Tensor,
@@ -370,19 +327,13 @@ def g1_kzg_open_evals_dev(d_lagrange: torch.Tensor, d_evals: torch.Tensor, exp: 
     rec = 104 if mont else 96
     if d_lagrange.numel() != rec << exp or d_evals.numel() != 32 << exp or d_out.numel() < 128:
         raise ValueError(f"kzg open evals: bad buffer sizes {d_lagrange.numel()} / {d_evals.numel()} / {d_out.numel()}")
-    if not all(t.is_cuda for t in (d_lagrange, d_evals, d_out, key)):
-        raise ValueError("g1_kzg_open_evals_dev needs device tensors")
     lib = _lib.load()
     flags = (1 if mont else 0) | (window << 8) | (tile << 16)
-    need = int(lib.kzgpot_kzg_open_evals_workspace(exp, flags))
-    if need == 0:
-        raise ValueError(f"kzg open evals: exp = {exp} with window {window}, tile {tile} is not supported")
-    work = _work(need, work, d_out.device, "kzg open evals")
-    rc = lib.kzgpot_g1_kzg_open_evals_dev(d_lagrange.data_ptr(), d_evals.data_ptr(), exp, int(z).to_bytes(32, "little"),
-                                          d_out.data_ptr(), flags, work.data_ptr(), key.data_ptr(), _stream())
-    if rc:
-        raise RuntimeError(f"kzg open evals: launch failed ({rc})")
-    return work
+    return _dev_call("kzg open evals", (d_out, d_lagrange, d_evals, key), int(lib.kzgpot_kzg_open_evals_workspace(exp, flags)),
+                     work, f"exp = {exp} with window {window}, tile {tile}",
+                     lambda w: lib.kzgpot_g1_kzg_open_evals_dev(
+                         d_lagrange.data_ptr(), d_evals.data_ptr(), exp, int(z).to_bytes(32, "little"), d_out.data_ptr(),
+                         flags, w.data_ptr(), key.data_ptr(), _stream()))
 
 
 GT_OUT_BYTES = 580  # 576 B of GT, then the u32 verdict
@@ -397,18 +348,10 @@ def pairing_product_dev(d_g1: torch.Tensor, d_g2: torch.Tensor, d_out: torch.Ten
     k = d_g1.numel() // 96
     if d_g1.numel() != 96 * k or d_g2.numel() != 192 * k or d_out.numel() < GT_OUT_BYTES:
         raise ValueError(f"pairing product: bad buffer sizes {d_g1.numel()} / {d_g2.numel()} / {d_out.numel()}")
-    if not all(t.is_cuda for t in (d_g1, d_g2, d_out, key)):
-        raise ValueError("pairing_product_dev needs device tensors")
     lib = _lib.load()
-    need = int(lib.kzgpot_pairing_workspace(k))
-    if need == 0:
-        raise ValueError(f"pairing product: k = {k} is not supported")
-    work = _work(need, work, d_out.device, "pairing product")
-    rc = lib.kzgpot_pairing_product_dev(d_g1.data_ptr() if k else None, d_g2.data_ptr() if k else None, k,
-                                        d_out.data_ptr(), work.data_ptr(), key.data_ptr(), _stream())
-    if rc:
-        raise RuntimeError(f"pairing product: launch failed ({rc})")
-    return work
+    return _dev_call("pairing product", (d_out, d_g1, d_g2, key), int(lib.kzgpot_pairing_workspace(k)), work, f"k = {k}",
+                     lambda w: lib.kzgpot_pairing_product_dev(d_g1.data_ptr() if k else None, d_g2.data_ptr() if k else None, k,
+                                                              d_out.data_ptr(), w.data_ptr(), key.data_ptr(), _stream()))
 
 
 def kzg_batch_check_dev(d_vk: torch.Tensor, d_commitments: torch.Tensor, d_points: torch.Tensor, d_values: torch.Tensor,
@@ -425,18 +368,11 @@ def kzg_batch_check_dev(d_vk: torch.Tensor, d_commitments: torch.Tensor, d_point
     if (d_vk.numel() != 576 or d_commitments.numel() != 96 * n or d_proofs_w.numel() != 96 * n
             or any(t.numel() != 32 * n for t in scalars) or d_out.numel() < GT_OUT_BYTES):
         raise ValueError(f"kzg batch check: bad buffer sizes for n = {n}")
-    if not all(t.is_cuda for t in [d_vk, d_commitments, d_proofs_w, d_out, key] + scalars):
-        raise ValueError("kzg_batch_check_dev needs device tensors")
     lib = _lib.load()
     flags = window << 8
-    need = int(lib.kzgpot_kzg_batch_check_workspace(n, flags))
-    if need == 0:
-        raise ValueError(f"kzg batch check: n = {n} with window {window} is not supported")
-    work = _work(need, work, d_out.device, "kzg batch check")
     ptr = lambda t: t.data_ptr() if t is not None and n else None  # noqa: E731
-    rc = lib.kzgpot_kzg_batch_check_dev(d_vk.data_ptr(), ptr(d_commitments), ptr(d_points), ptr(d_values), ptr(d_proofs_w),
-                                        ptr(d_random_vs), ptr(d_randomizers), n, d_out.data_ptr(), flags,
-                                        work.data_ptr(), key.data_ptr(), _stream())
-    if rc:
-        raise RuntimeError(f"kzg batch check: launch failed ({rc})")
-    return work
+    return _dev_call("kzg batch check", [d_out, d_vk, d_commitments, d_proofs_w, key] + scalars,
+                     int(lib.kzgpot_kzg_batch_check_workspace(n, flags)), work, f"n = {n} with window {window}",
+                     lambda w: lib.kzgpot_kzg_batch_check_dev(
+                         d_vk.data_ptr(), ptr(d_commitments), ptr(d_points), ptr(d_values), ptr(d_proofs_w), ptr(d_random_vs),
+                         ptr(d_randomizers), n, d_out.data_ptr(), flags, w.data_ptr(), key.data_ptr(), _stream()))
