@@ -1,7 +1,8 @@
 // Device functions that the group kernels (fft_kernels.hip: the group FFT; msm_kernels.hip: the
 // multi-scalar multiplication) share, each stated once: the limb-major work rows, the ark record
 // decode with the loaders' checks, the canonical-value helpers for both fields, the Jacobian ->
-// affine conversion and the record emit. All force-inlined.
+// affine tail (jac_to_affine: the one statement of "zero test, canonicalise, invert Z, scale") and
+// the record emit. All force-inlined.
 //
 // Work rows: limb-major rows of `m` words, row k holding word k of every point (a wave's accesses
 // to one row are contiguous wherever its points are): x (NW rows), y (NW rows), then one row that
@@ -68,6 +69,11 @@ KZG_DEV void work_load(F& a, const uint32_t* work, uint64_t m, int row, uint64_t
   for (int k = 0; k < Geo<F>::NW; k++) d[k] = work[(uint64_t)(row + k) * m + idx];
 }
 template <typename F>
+KZG_DEV void work_load_xy(F& x, F& y, const uint32_t* work, uint64_t m, uint64_t idx) {
+  work_load(x, work, m, 0, idx);
+  work_load(y, work, m, Geo<F>::NW, idx);
+}
+template <typename F>
 KZG_DEV void work_store(uint32_t* work, uint64_t m, int row, uint64_t idx, const F& a) {
   const uint32_t* s = (const uint32_t*)&a;
 #pragma unroll
@@ -116,10 +122,13 @@ KZG_DEV int ark_record_decode(F& x, F& y, bool& finf, const uint4* rec) {
   if (!st && both) st = 6;
   if (!st && words_geq_p(w[2 * NC - 1])) st = 3;
   if (st) return st;
-#pragma unroll
-  for (int c = 0; c < NC; c++) {
-    words_to_mont(comp(x, c), w[c]);
-    words_to_mont(comp(y, c), w[NC + c]);
+  // written out: as a loop the four Fp2 conversions are past the unroller's size limit, and a loop
+  // left rolled indexes w dynamically, which puts it into scratch
+  words_to_mont(comp(x, 0), w[0]);
+  words_to_mont(comp(y, 0), w[NC]);
+  if constexpr (NC == 2) {
+    words_to_mont(x.c1, w[1]);
+    words_to_mont(y.c1, w[3]);
   }
   f_reduce_once(x);
   f_reduce_once(y);
@@ -145,6 +154,39 @@ KZG_DEV void scale_to_affine(F& x, F& y, const F& X, const F& Y, const F& zi, bo
     f_zero(x);
     f_zero(y);
   }
+}
+
+template <typename F>
+KZG_DEV void jac_set_infinity(jac<F>& acc) {  // X = Y = Z = 0: jac_dbl keeps it, jac_madd replaces it by its operand
+  f_zero(acc.x);
+  f_zero(acc.y);
+  f_zero(acc.z);
+}
+template <typename F>
+KZG_DEV void jac_canon(jac<F>& acc) {
+  f_canon(acc.x);
+  f_canon(acc.y);
+  f_canon(acc.z);
+}
+// a canonical accumulator and its infinity flag -> canonical affine (x, y), zero if inf: Z (1 for
+// an infinite one) inverted once. With a constant inf = false the selects fold away.
+template <typename F>
+KZG_DEV void canon_jac_to_affine(F& x, F& y, jac<F>& acc, bool inf) {
+  F one, zi;
+  f_one(one);
+  f_select(acc.z, inf, one, acc.z);
+  f_inv(zi, acc.z);
+  f_reduce_once(zi);
+  scale_to_affine(x, y, acc.x, acc.y, zi, inf);
+}
+// an accumulator as a ladder or a mixed addition left it -> canonical affine; returns whether it
+// is the point at infinity (Z = 0, tested before Z is canonicalised)
+template <typename F>
+KZG_DEV bool jac_to_affine(F& x, F& y, jac<F>& acc) {
+  const bool inf = f_is_zero(acc.z);
+  jac_canon(acc);
+  canon_jac_to_affine(x, y, acc, inf);
+  return inf;
 }
 
 // ---------------------------------------------------------------- emit

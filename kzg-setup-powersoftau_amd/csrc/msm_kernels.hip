@@ -31,8 +31,9 @@
 // Where every launch reads and writes inside the workspace, and the list of k_msm_sum launches, is
 // msm_plan's (plans.hpp, checked on the CPU by tests/test_plan_units.py).
 //
-// Between two additions X, Y and Z go through fp_canon, so every jac_madd starts from a canonical
-// accumulator (or Z = 0) and a canonical base: tests/test_field_bounds_msm.py.
+// Between two additions X, Y and Z go through fp_canon (jac_canon), so every jac_madd starts from a
+// canonical accumulator (or Z = 0) and a canonical base: tests/test_field_bounds_msm.py. A chunk's
+// sum and the final result become affine by group_parts.hpp's canon_jac_to_affine.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -224,7 +225,7 @@ struct SumArgs {
 template <typename F>
 __global__ void __launch_bounds__(Geo<F>::BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_msm_sum(uint32_t* pool, uint64_t cap, SumArgs a, const unsigned long long* __restrict__ key) {
-  constexpr int NW = Geo<F>::NW, BLOCK = Geo<F>::BLOCK, INF = Geo<F>::INF_ROW;
+  constexpr int BLOCK = Geo<F>::BLOCK, INF = Geo<F>::INF_ROW;
   if (rejected(key)) return;
   const uint64_t q = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
   uint32_t start, end, seg = 0;
@@ -264,34 +265,19 @@ k_msm_sum(uint32_t* pool, uint64_t cap, SumArgs a, const unsigned long long* __r
   };
 
   jac<F> acc;
-  f_zero(acc.x);
-  f_zero(acc.y);
-  f_zero(acc.z);  // the point at infinity: jac_madd replaces it by its operand
+  jac_set_infinity(acc);
   int adds = 0;
 #pragma unroll 1
   for (uint32_t e = start; e < end; e++) {
     const uint64_t s = slot_of(e);
     if (s == kNoSlot) continue;
-    jac_madd(acc, [&](F& x, F& y) {
-      const uint32_t* w = opaque(rd);
-      work_load(x, w, cap, 0, s);
-      work_load(y, w, cap, NW, s);
-    });
-    f_canon(acc.x);
-    f_canon(acc.y);
-    f_canon(acc.z);
+    jac_madd(acc, [&](F& x, F& y) { work_load_xy(x, y, opaque(rd), cap, s); });
+    jac_canon(acc);
     adds++;
   }
   const bool inf = f_is_zero(acc.z);
   F x = acc.x, y = acc.y;
-  if (adds > 1) {  // one entry: Z = 1 and (X, Y) is the entry
-    F one, zi;
-    f_one(one);
-    f_select(acc.z, inf, one, acc.z);
-    f_inv(zi, acc.z);
-    f_reduce_once(zi);
-    scale_to_affine(x, y, acc.x, acc.y, zi, inf);
-  }
+  if (adds > 1) canon_jac_to_affine(x, y, acc, inf);  // one entry: Z = 1 and (X, Y) is the entry
   work_store_point(pool, cap, a.out_base + q, x, y, inf);
 }
 
@@ -302,34 +288,24 @@ template <typename F>
 __global__ void __launch_bounds__(64) k_msm_final(const uint32_t* __restrict__ pool, uint64_t cap, uint64_t in_base,
                                                   int nbits, uint4* __restrict__ out,
                                                   const unsigned long long* __restrict__ key) {
-  constexpr int NW = Geo<F>::NW, INF = Geo<F>::INF_ROW;
+  constexpr int INF = Geo<F>::INF_ROW;
   if (rejected(key) || threadIdx.x || blockIdx.x) return;
   jac<F> acc;
-  f_zero(acc.x);
-  f_zero(acc.y);
-  f_zero(acc.z);
+  jac_set_infinity(acc);
 #pragma unroll 1
   for (int k = nbits - 1; k >= 0; k--) {
     jac_dbl(acc);
     const uint64_t s = in_base + (uint64_t)k;
     if (opaque(pool)[(uint64_t)INF * cap + s]) continue;
-    jac_madd(acc, [&](F& x, F& y) {
-      const uint32_t* w = opaque(pool);
-      work_load(x, w, cap, 0, s);
-      work_load(y, w, cap, NW, s);
-    });
+    jac_madd(acc, [&](F& x, F& y) { work_load_xy(x, y, opaque(pool), cap, s); });
   }
   if (f_is_zero(acc.z)) {
     emit_infinity<F>(out, false);
     return;
   }
-  f_canon(acc.x);
-  f_canon(acc.y);
-  f_canon(acc.z);
-  F zi, x, y;
-  f_inv(zi, acc.z);
-  f_reduce_once(zi);
-  scale_to_affine(x, y, acc.x, acc.y, zi, false);
+  jac_canon(acc);
+  F x, y;
+  canon_jac_to_affine(x, y, acc, false);
   emit_point(out, x, y, false);
 }
 

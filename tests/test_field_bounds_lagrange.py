@@ -1,5 +1,5 @@
 """Limb / value bounds of the group FFT's butterfly (csrc/fft_kernels.hip k_fft_stage, k_h_bases,
-k_fft_emit), with tests/field_bounds_model.py unchanged.
+k_fft_point_mul, k_fft_emit), with tests/field_bounds_model.py unchanged.
 
 The ladder [w]Q is jac_dbl + jac_madd from a canonical base, so its states lie in the ladder bound
 set S that test_field_bounds.py proves closed under "double, then optionally add the base" for any
@@ -52,13 +52,24 @@ def inv_fp(a, name="inv"):
     return M.mul(t, a, name)
 
 
-def to_affine_fp(X, Y, zi):
-    """fft_kernels.hip scale_to_affine over Fp: canonical X, Y, zi -> canonical x, y."""
+def scale_to_affine_fp(X, Y, zi):
+    """group_parts.hpp scale_to_affine over Fp: canonical X, Y, zi -> canonical x, y."""
     z2 = M.sqr(zi, "zi2")
     x = reduce_once(M.mul(X, z2, "x"), "x")
     z3 = M.mul(z2, zi, "zi3")
     y = reduce_once(M.mul(Y, z3, "y"), "y")
-    return x, neg_canon(y, "-y")  # out1's y is negated (P - T = -(T - P))
+    return x, y
+
+
+def canon_jac_to_affine_fp(X, Y, Z):
+    """group_parts.hpp canon_jac_to_affine over Fp, the one Jacobian -> affine tail of the scale /
+    per-point pass (k_fft_point_mul), k_h_bases, k_msm_sum and k_msm_final: canonical X, Y and Z
+    (an infinite Z replaced by the canonical 1), one inversion, scale_to_affine; the result is
+    canonical and fits the emit's from-Montgomery input."""
+    zi = reduce_once(inv_fp(Z), "1/Z")
+    x, y = scale_to_affine_fp(X, Y, zi)
+    M.from_mont_ok(x, "emit x"), M.from_mont_ok(y, "emit y")
+    return x, y
 
 
 def test_g1_butterfly_bounds():
@@ -66,8 +77,9 @@ def test_g1_butterfly_bounds():
     base = M.normalized(Fraction(101, 100))  # the work buffer holds canonical values: a subset
     S = M.ladder_invariant(F, base, base)
     M.jac_eq_affine(F, *S, base, base)  # the set test_field_bounds.py proves
-    for v in S:  # T itself is canonicalised when P is infinite, and in the 1/m scale pass
+    for v in S:  # T itself is canonicalised when P is infinite, and in the scale / per-point pass
         canon(v, "T")
+    canon_jac_to_affine_fp(canonical("T.X"), canonical("T.Y"), canonical("T.Z"))  # k_fft_point_mul
     ny = neg_canon(canonical("P.y"))
     for py in (canonical("P.y"), ny):  # R0 = T + P, R1 = T + (-P), from any ladder state
         R = M.jac_madd(F, *S, canonical("P.x"), py)
@@ -79,9 +91,9 @@ def test_g1_butterfly_bounds():
     zi0 = reduce_once(M.mul(zi, z1, "zi0"))
     zi1 = reduce_once(M.mul(zi, z0, "zi1"))
     for z in (zi0, zi1):
-        x, y = to_affine_fp(X, Y, z)
+        x, y = scale_to_affine_fp(X, Y, z)
         M.from_mont_ok(x, "emit x")  # k_fft_emit
-        M.from_mont_ok(y, "emit y")
+        M.from_mont_ok(neg_canon(y, "-y"), "emit y")  # out1's y is negated (P - T = -(T - P))
 
 
 def test_g1_load_and_h_bases_bounds():
@@ -92,10 +104,7 @@ def test_g1_load_and_h_bases_bounds():
     xm = M.mul(canonical("x"), canonical("R2"), "to_mont")
     reduce_once(xm, "load")
     R = M.jac_madd(F, xm, xm, M.normalized(1), xm, neg_canon(reduce_once(xm)))
-    X, Y, Z = (canon(v, "h") for v in R)
-    zi = reduce_once(inv_fp(Z), "1/Z")
-    x, y = to_affine_fp(X, Y, zi)
-    M.from_mont_ok(x), M.from_mont_ok(y)
+    canon_jac_to_affine_fp(*(canon(v, "h") for v in R))
 
 
 def _v2(v):
@@ -115,12 +124,32 @@ def reduce_once2(a, name="reduce_once2"):
     return M.V2(reduce_once(a.c0, name), reduce_once(a.c1, name))
 
 
+def scale_to_affine_fp2(X, Y, zi):
+    """group_parts.hpp scale_to_affine over Fp2, in the reduced discipline (f_mul / f_sqr)."""
+    z2 = M.f2_sqr(zi, "zi2")
+    x = reduce_once2(M.f2_mul(X, z2, "x"))
+    z3 = M.f2_mul(z2, zi, "zi3")
+    y = reduce_once2(M.f2_mul(Y, z3, "y"))
+    return x, y
+
+
+def canon_jac_to_affine_fp2(X, Y, Z):
+    """group_parts.hpp canon_jac_to_affine over Fp2: as canon_jac_to_affine_fp, per component."""
+    zi = reduce_once2(inv_fp2(Z), "1/Z")
+    x, y = scale_to_affine_fp2(X, Y, zi)
+    for c in (x.c0, x.c1, y.c0, y.c1):
+        M.from_mont_ok(c, "emit")
+    return x, y
+
+
 def test_g2_butterfly_bounds():
     base = _v2(M.normalized(Fraction(101, 100)))
     S = M.ladder_invariant_fp2_lz(base, base)
     M.jac_eq_affine_fp2_lz(*S, base, base)
     for v in S:
         canon(v.c0, "T.c0"), canon(v.c1, "T.c1")
+    T = _v2(canonical("T"))
+    canon_jac_to_affine_fp2(T, T, T)  # k_fft_point_mul
     P = _v2(canonical("P"))
     nP = M.V2(neg_canon(P.c0), neg_canon(P.c1))
     for py in (P, nP):
@@ -132,10 +161,7 @@ def test_g2_butterfly_bounds():
     zz = reduce_once2(M.f2_mul(z0, z1, "Z0Z1"))
     zi = reduce_once2(inv_fp2(zz), "1/(Z0Z1)")
     zi0 = reduce_once2(M.f2_mul(zi, z1, "zi0"))
-    z2 = M.f2_sqr(zi0, "zi2")
-    x = reduce_once2(M.f2_mul(X, z2, "x"))
-    z3 = M.f2_mul(z2, zi0, "zi3")
-    y = reduce_once2(M.f2_mul(Y, z3, "y"))
+    x, y = scale_to_affine_fp2(X, Y, zi0)
     for c in (x.c0, x.c1, neg_canon(y.c0), neg_canon(y.c1)):
         M.from_mont_ok(c, "emit")
     # k_fft_load: as for G1, per component

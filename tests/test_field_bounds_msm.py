@@ -8,14 +8,14 @@ after every addition, and what is shown here without a BoundError is one link of
     empty sum) with a canonical base — M.jac_madd joins the equal-point branch's jac_dbl outputs
     into its result, and jac_dbl from the same inputs is run on its own as well — every output
     passing fp_canon's input condition;
-  * the normalisation of a chunk's sum and of the final result: inversion of a canonical Z,
-    x = X z^-2, y = Y z^-3, one conditional subtraction each, and the emit's from-Montgomery input;
+  * the normalisation of a chunk's sum and of the final result: group_parts.hpp's
+    canon_jac_to_affine, as test_field_bounds_lagrange.py states it once per field;
   * k_msm_final's ladder: jac_dbl, then jac_madd of a canonical base — the proven ladder set, from
     Z = 0, its states canonicalised at the end;
   * k_msm_load's two inputs: a range-checked coordinate to Montgomery form (as k_fft_load), and an
     ark-ff Montgomery image (R = 2^384, < p) times FP_FROM_ARK = 2^400 mod p."""
 import field_bounds_model as M
-from test_field_bounds_lagrange import _v2, canon, canonical, inv_fp, inv_fp2, reduce_once, reduce_once2
+from test_field_bounds_lagrange import _v2, canon, canon_jac_to_affine_fp, canon_jac_to_affine_fp2, canonical, reduce_once
 
 
 def zero():
@@ -49,22 +49,13 @@ def test_g2_chained_addition_link():
 
 
 def test_g1_normalisation():
-    X, Y, Z = canonical("X"), canonical("Y"), canonical("Z")
-    zi = reduce_once(inv_fp(Z), "1/Z")
-    z2 = M.sqr(zi, "zi2")
-    x = reduce_once(M.mul(X, z2, "x"), "x")
-    y = reduce_once(M.mul(Y, M.mul(z2, zi, "zi3"), "y"), "y")
-    M.from_mont_ok(x, "emit x"), M.from_mont_ok(y, "emit y")
+    """A chunk's sum (k_msm_sum) and the final result (k_msm_final): the shared tail."""
+    canon_jac_to_affine_fp(canonical("X"), canonical("Y"), canonical("Z"))
 
 
 def test_g2_normalisation():
     X = Y = Z = _v2(canonical())
-    zi = reduce_once2(inv_fp2(Z), "1/Z")
-    z2 = M.f2_sqr(zi, "zi2")
-    x = reduce_once2(M.f2_mul(X, z2, "x"))
-    y = reduce_once2(M.f2_mul(Y, M.f2_mul(z2, zi, "zi3"), "y"))
-    for c in (x.c0, x.c1, y.c0, y.c1):
-        M.from_mont_ok(c, "emit")
+    canon_jac_to_affine_fp2(X, Y, Z)
 
 
 def test_final_ladder_is_the_proven_set():
