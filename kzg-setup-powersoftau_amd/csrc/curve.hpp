@@ -192,9 +192,8 @@ KZG_DEV void jac_madd_w(jac<f30>& p, Load&& load) {
 // The G1 discipline on both components: limb-wise adds and borrowed-constant subtractions, an
 // fp_norm only where the next multiply needs normalized limbs — instead of the reduced (< 2p)
 // helpers' serial borrow / carry / conditional-2p chains (~125 instructions each, 24 per
-// doubling). Every constant is the one tests/field_bounds_model.py (jac_dbl_fp2_lz,
-// jac_madd_fp2_lz, jac_eq_affine_fp2_lz) proves for all inputs; ladder states stay normalized
-// with values below ~21 p.
+// doubling). Every constant is the one tests/field_bounds_model.py (jac_dbl_fp2, jac_madd_fp2,
+// jac_eq_affine_fp2) proves for all inputs; ladder states stay normalized with values below ~21 p.
 // r = a b with b.c1 negated against k (k must dominate b.c1): two Montgomery reductions
 template <const auto& K>
 KZG_DEV void f2_mul_lz(fp2& r, const fp2& a, const fp2& b) {
@@ -233,20 +232,40 @@ KZG_DEV void f2_norm(fp2& r, const fp2& a) {
   fp_norm(r.c1, a.c1);
 }
 
-// G2 doubling (63 per point): X, Y, Z normalized in and out. 3 squarings + 2 multiplies in Fp2,
-// and Y3 = E (D - X3) - 8 B^2 with C = B^2 folded into E's product as in the G1 doubling: per
-// component one three-product reduction,
+// G2 doubling and mixed addition, each stated once for the two coordinate forms: jac_dbl(p) /
+// jac_madd(p, load), W = false, carry Y (in_subgroup_ref<fp2>, the group FFT, the MSM and the
+// generator); jac_dbl<true> / jac_madd<true> carry W = 2Y (the fast ladder, mul_abs_u_affine<fp2>), as
+// the G1 W form (jac_dbl_w(jac<f30>&) above). The W form has no forwarding jac_dbl_w / jac_madd_w
+// name: one more level of inlining reorders the multiplies' mad chains in every G2 kernel. Where
+// the forms differ the comment says why. Bounds: tests/field_bounds_model.py jac_dbl_fp2 /
+// jac_madd_fp2 (its w is this W) / jac_tpl_affine_fp2_w / ladder_invariant_fp2.
+//
+// Doubling (63 per point in the fast ladder): X, Y, Z normalized in and out. 3 squarings + 2
+// multiplies in Fp2, and Y3 = E (D - X3) - 8 B^2 with C = B^2 folded into E's product as in the G1
+// doubling: per component one three-product reduction,
 //   Y3.c0 = e0 t0 + e1 (-t1) + (b0 + b1) (-8 (b0 - b1)),   Y3.c1 = e0 t1 + e1 t0 + (2 b0) (-8 b1)
 // (t = D - X3; the negated factors normalized so every product stays below 2^58) — 1,568 product
 // MACs and 2 reductions where C's squaring plus E (D - X3) took 1,960 and 4.
+// W form: B' = W^2 = 4B, so D = X B' and Z3 = W Z need no 4X / 2Y, and W3 = (2E)(D - X3) - B'^2 needs
+// no -8 scaling of B^2's factors.
+template <bool W = false>
 KZG_DEV void jac_dbl(jac<fp2>& p) {
   fp2 b, a, d, t;
-  f2_sqr_lz<BlsFp::KB_32_28>(b, p.y);        // B = Y^2
-  f2_shl<1>(t, p.y);
-  f2_mul_lz<BlsFp::KB_16_28>(p.z, t, p.z);   // Z3 = 2 Y Z          (Y dead)
+  if constexpr (W) {
+    f2_sqr_lz<BlsFp::KB_32_29>(b, p.y);      // B' = W^2: W limbs reach 2^29 (the base's w = 2y), so KB_*_29
+    f2_mul_lz<BlsFp::KB_16_28>(p.z, p.y, p.z);  // Z3 = W Z          (W dead)
+  } else {
+    f2_sqr_lz<BlsFp::KB_32_28>(b, p.y);      // B = Y^2
+    f2_shl<1>(t, p.y);
+    f2_mul_lz<BlsFp::KB_16_28>(p.z, t, p.z); // Z3 = 2 Y Z          (Y dead)
+  }
   f2_sqr_lz<BlsFp::KB_16_28>(a, p.x);        // A = X^2
-  f2_shl<2>(t, p.x);
-  f2_mul_lz<BlsFp::KB_2_28>(d, t, b);        // D = 4 X B           (X dead)
+  if constexpr (W) {
+    f2_mul_lz<BlsFp::KB_2_28>(d, p.x, b);    // D = X B'            (X dead)
+  } else {
+    f2_shl<2>(t, p.x);
+    f2_mul_lz<BlsFp::KB_2_28>(d, t, b);      // D = 4 X B           (X dead)
+  }
   fp_mul3_nr(a.c0, a.c0);
   fp_mul3_nr(a.c1, a.c1);
   f2_norm(a, a);                             // E = 3 A             (A dead)
@@ -255,26 +274,36 @@ KZG_DEV void jac_dbl(jac<fp2>& p) {
   f2_subk<BlsFp::KB_4_29>(p.x, t, p.x);
   f2_norm(p.x, p.x);                         // X3 = F - 2D         (F dead)
   f2_subk<BlsFp::KB_8_28>(d, d, p.x);        // t = D - X3
+  if constexpr (W) f2_shl<1>(a, a);          // 2E: W3 = 2 Y3
   fp u, s, n, c0;
   fp_negk_nr<BlsFp::KB_16_30>(u, d.c1);      // -t1
   fp_add_nr(s, b.c0, b.c1);                  // b0 + b1             < 2^29
-  fp_subk_nr<BlsFp::KB_2_28>(n, b.c0, b.c1);
-  fp_norm(n, n);                             // b0 - b1             N
-  fp_shl_nr<3>(n, n);
-  fp_negk_nr<BlsFp::KB_64_31>(n, n);
-  fp_norm(n, n);                             // -8 (b0 - b1)        N
+  if constexpr (W) {                         // B'^2 = 16 B^2 is W3's own term: its factors unscaled
+    fp_subk_nr<BlsFp::KB_2_28>(n, b.c1, b.c0);
+    fp_norm(n, n);                           // b1 - b0             N
+  } else {
+    fp_subk_nr<BlsFp::KB_2_28>(n, b.c0, b.c1);
+    fp_norm(n, n);                           // b0 - b1             N
+    fp_shl_nr<3>(n, n);
+    fp_negk_nr<BlsFp::KB_64_31>(n, n);
+    fp_norm(n, n);                           // -8 (b0 - b1)        N
+  }
   fp_mul_sum3(c0, a.c0, d.c0, a.c1, u, s, n);
-  fp_shl_nr<3>(n, b.c1);
-  fp_negk_nr<BlsFp::KB_16_31>(n, n);
-  fp_norm(n, n);                             // -8 b1               N
+  if constexpr (W) {
+    fp_negk_nr<BlsFp::KB_2_28>(n, b.c1);     // -b1                 < 2^29
+  } else {
+    fp_shl_nr<3>(n, b.c1);
+    fp_negk_nr<BlsFp::KB_16_31>(n, n);
+    fp_norm(n, n);                           // -8 b1               N
+  }
   fp_shl_nr<1>(s, b.c0);                     // 2 b0                < 2^29
   fp_mul_sum3(p.y.c1, a.c0, d.c1, a.c1, d.c0, s, n);
-  p.y.c0 = c0;                               // Y3 = E (D - X3) - 8 B^2
+  p.y.c0 = c0;                               // Y3 = E (D - X3) - 8 B^2;  W3 = 2E (D - X3) - B'^2
 }
 
-// G2 mixed addition (ark add_assign_mixed incl. its zero / equal-point branches, as jac_madd):
-// X, Y, Z normalized in and out; the base point (x2, y2) normalized, values < 1.01 p.
-template <typename Load>
+// Mixed addition (ark add_assign_mixed incl. its zero / equal-point branches, as the generic jac_madd):
+// X, Y, Z normalized in and out; the base point (x2, y2) normalized, values < 1.01 p (W: y2 = 2y).
+template <bool W = false, typename Load>
 KZG_DEV void jac_madd(jac<fp2>& p, Load&& load) {
   fp2 z1z1, h, r, t;
   {
@@ -285,15 +314,18 @@ KZG_DEV void jac_madd(jac<fp2>& p, Load&& load) {
     f2_subk<BlsFp::KB_32_28>(h, h, p.x);
     f2_norm(h, h);                           // H = U2 - X1
     f2_mul_lz<BlsFp::KB_16_28>(t, y2, p.z);
-    f2_mul_lz<BlsFp::KB_2_28>(t, t, z1z1);   // S2
-    f2_subk<BlsFp::KB_32_28>(r, t, p.y);
-    f2_norm(r, r);                           // r' = S2 - Y1   (ark's r = 2 r')
+    f2_mul_lz<BlsFp::KB_2_28>(t, t, z1z1);   // S2  (W: 2 S2)
+    if constexpr (W)
+      f2_subk<BlsFp::KB_32_29>(r, t, p.y);   // r = 2 S2 - W1 = 2 (S2 - Y1) is ark's r; KB_*_29 against W
+    else
+      f2_subk<BlsFp::KB_32_28>(r, t, p.y);   // r' = S2 - Y1   (ark's r = 2 r')
+    f2_norm(r, r);
   }
   const bool z1zero = f_is_zero(p.z);
   const bool same = !z1zero && f_is_zero(h) && f_is_zero(r);
   if (__builtin_expect(z1zero || same, 0)) {
     if (same) {
-      jac_dbl(p);
+      jac_dbl<W>(p);
     } else {
       load(p.x, p.y);
       f_one(p.z);
@@ -307,53 +339,20 @@ KZG_DEV void jac_madd(jac<fp2>& p, Load&& load) {
   f2_shl<2>(hh, hh);                         // I = 4 HH
   f2_mul_lz<BlsFp::KB_8_30>(j, h, hh);       // J = H I
   f2_mul_lz<BlsFp::KB_8_30>(hh, p.x, hh);    // V = X1 I
-  f2_sqr_lz<BlsFp::KB_64_28>(t, r);          // r'^2
-  f2_shl<2>(t, t);                           // r^2 = 4 r'^2
+  f2_sqr_lz<BlsFp::KB_64_28>(t, r);          // r'^2  (W: r^2)
+  if constexpr (!W) f2_shl<2>(t, t);         // r^2 = 4 r'^2; the W form's r is ark's: no 4 r'^2
   f2_subk<BlsFp::KB_2_28>(t, t, j);
   f2_shl<1>(h, hh);                          // 2V
   f2_subk<BlsFp::KB_4_29>(t, t, h);
   f2_norm(t, t);                             // X3 = r^2 - J - 2V
   f2_subk<BlsFp::KB_32_28>(hh, hh, t);       // V - X3
-  f2_shl<1>(r, r);                           // r = 2 r'
+  f2_shl<1>(r, r);                           // r = 2 r'  (W: 2r)
   f2_mul_lz<BlsFp::KB_64_30>(hh, r, hh);     // r (V - X3)
   f2_shl<1>(h, p.y);                         // 2 Y1
   f2_mul_lz<BlsFp::KB_2_28>(j, h, j);        // 2 Y1 J
   f2_subk<BlsFp::KB_4_28>(p.y, hh, j);
-  f2_norm(p.y, p.y);                         // Y3 = r (V - X3) - 2 Y1 J
+  f2_norm(p.y, p.y);                         // Y3 = r (V - X3) - 2 Y1 J;  W3 = 2 Y3 = 2r (V - X3) - 2 W1 J
   p.x = t;
-}
-
-// ---------------------------------------------------------------- G2 fast ladder, W = 2Y
-// As the G1 W form (jac_dbl_w(jac<f30>&) above): B' = W^2, D = X B' and Z3 = W Z need no 4X / 2Y, and
-// W3 = (2E)(D - X3) - B'^2 needs no -8 scaling of B^2's factors; the mixed addition's
-// r = 2 S2 - W1 is ark's r. W limbs reach 2^29 (the base's w = 2y), so the constants borrowed
-// against W are KB_*_29. Bounds: tests/field_bounds_model.py jac_dbl_fp2_w / jac_madd_fp2_w /
-// jac_tpl_affine_fp2_w / ladder_invariant_fp2_w.
-KZG_DEV void jac_dbl_w(jac<fp2>& p) {
-  fp2 b, a, d, t;
-  f2_sqr_lz<BlsFp::KB_32_29>(b, p.y);        // B' = W^2
-  f2_mul_lz<BlsFp::KB_16_28>(p.z, p.y, p.z); // Z3 = W Z           (W dead)
-  f2_sqr_lz<BlsFp::KB_16_28>(a, p.x);        // A = X^2
-  f2_mul_lz<BlsFp::KB_2_28>(d, p.x, b);      // D = X B'           (X dead)
-  fp_mul3_nr(a.c0, a.c0);
-  fp_mul3_nr(a.c1, a.c1);
-  f2_norm(a, a);                             // E = 3 A            (A dead)
-  f2_sqr_lz<BlsFp::KB_4_28>(t, a);           // F = E^2
-  f2_shl<1>(p.x, d);
-  f2_subk<BlsFp::KB_4_29>(p.x, t, p.x);
-  f2_norm(p.x, p.x);                         // X3 = F - 2D        (F dead)
-  f2_subk<BlsFp::KB_8_28>(d, d, p.x);        // t = D - X3
-  f2_shl<1>(a, a);                           // 2E
-  fp u, s, n, c0;
-  fp_negk_nr<BlsFp::KB_16_30>(u, d.c1);      // -t1
-  fp_add_nr(s, b.c0, b.c1);                  // b0 + b1             < 2^29
-  fp_subk_nr<BlsFp::KB_2_28>(n, b.c1, b.c0);
-  fp_norm(n, n);                             // b1 - b0             N
-  fp_mul_sum3(c0, a.c0, d.c0, a.c1, u, s, n);
-  fp_negk_nr<BlsFp::KB_2_28>(n, b.c1);       // -b1                 < 2^29
-  fp_shl_nr<1>(s, b.c0);                     // 2 b0                < 2^29
-  fp_mul_sum3(p.y.c1, a.c0, d.c1, a.c1, d.c0, s, n);
-  p.y.c0 = c0;                               // W3 = 2E (D - X3) - B'^2
 }
 
 // The scaled triple (X3/4, W3/8, E) of 3P from (x, w = 2y): YYw = w^2, T = YYw^2, E = 3 x YYw - MM,
@@ -396,57 +395,10 @@ KZG_DEV void jac_tpl_affine_w(jac<fp2>& p, Load&& load) {
   f2_mul_lz<BlsFp::KB_8_28>(p.y, p.y, t);    // W3 / 8 = w (U (T - U) - E EE)
 }
 
-template <typename Load>
-KZG_DEV void jac_madd_w(jac<fp2>& p, Load&& load) {
-  fp2 z1z1, h, r, t;
-  {
-    fp2 x2, w2;
-    load(x2, w2);
-    f2_sqr_lz<BlsFp::KB_16_28>(z1z1, p.z);
-    f2_mul_lz<BlsFp::KB_2_28>(h, x2, z1z1);  // U2
-    f2_subk<BlsFp::KB_32_28>(h, h, p.x);
-    f2_norm(h, h);                           // H = U2 - X1
-    f2_mul_lz<BlsFp::KB_16_28>(t, w2, p.z);
-    f2_mul_lz<BlsFp::KB_2_28>(t, t, z1z1);   // 2 S2
-    f2_subk<BlsFp::KB_32_29>(r, t, p.y);
-    f2_norm(r, r);                           // r = 2 S2 - W1 = 2 (S2 - Y1)
-  }
-  const bool z1zero = f_is_zero(p.z);
-  const bool same = !z1zero && f_is_zero(h) && f_is_zero(r);
-  if (__builtin_expect(z1zero || same, 0)) {
-    if (same) {
-      jac_dbl_w(p);
-    } else {
-      load(p.x, p.y);
-      f_one(p.z);
-    }
-    return;
-  }
-  fp2 hh, j;
-  f2_sqr_lz<BlsFp::KB_64_28>(hh, h);         // HH
-  f2_shl<1>(t, p.z);
-  f2_mul_lz<BlsFp::KB_64_28>(p.z, t, h);     // Z3 = 2 Z1 H
-  f2_shl<2>(hh, hh);                         // I = 4 HH
-  f2_mul_lz<BlsFp::KB_8_30>(j, h, hh);       // J = H I
-  f2_mul_lz<BlsFp::KB_8_30>(hh, p.x, hh);    // V = X1 I
-  f2_sqr_lz<BlsFp::KB_64_28>(t, r);          // r^2
-  f2_subk<BlsFp::KB_2_28>(t, t, j);
-  f2_shl<1>(h, hh);                          // 2V
-  f2_subk<BlsFp::KB_4_29>(t, t, h);
-  f2_norm(t, t);                             // X3 = r^2 - J - 2V
-  f2_subk<BlsFp::KB_32_28>(hh, hh, t);       // V - X3
-  f2_shl<1>(r, r);                           // 2r
-  f2_mul_lz<BlsFp::KB_64_30>(hh, r, hh);     // 2r (V - X3)
-  f2_shl<1>(h, p.y);                         // 2 W1
-  f2_mul_lz<BlsFp::KB_2_28>(j, h, j);        // 2 W1 J
-  f2_subk<BlsFp::KB_4_28>(p.y, hh, j);
-  f2_norm(p.y, p.y);                         // W3 = 2r (V - X3) - 2 W1 J
-  p.x = t;
-}
-
 // ---------------------------------------------------------------- mixed addition (cold)
 // ark add_assign_mixed: p += (x2, y2) for a finite affine (x2, y2) that `load(x2, y2)` delivers
-// (normalized, v <= 2 — or, for the G1 test's second ladder, a ladder state: limbs < 2^30). The
+// (normalized, v <= 2, at every call site: the parked point of in_subgroup_ref, a work row of the
+// group FFT or the MSM, a converted record of k_h_bases, the generator or a table point). The
 // base point is fetched inside and dies after U2 / S2 (the rare `self.is_zero()` branch fetches it
 // again), so it never occupies registers across the formula.
 // In: X, Y limbs < 2^30, values <= 40; Z normalized. Out: normalized, values <= 64.
@@ -521,8 +473,8 @@ KZG_DEV void mul_abs_u_affine(jac<F>& acc, Load&& load) {
     jac_tpl_affine_w(acc, loadw);
 #pragma unroll 1
     for (int b = BLS_ABS_U_BITS - 3; b >= 0; b--) {
-      jac_dbl_w(acc);
-      if ((BLS_ABS_U >> b) & 1) jac_madd_w(acc, loadw);
+      jac_dbl<true>(acc);  // <true>: the W form
+      if ((BLS_ABS_U >> b) & 1) jac_madd<true>(acc, loadw);
     }
   }
 }

@@ -32,7 +32,6 @@ constexpr int arity(int op) {
     case KZGPOT_FP_MUL_SUM3: return 6;
     case KZGPOT_FP_MUL_SUM2:
     case KZGPOT_FP_F2_MUL: return 4;
-    case KZGPOT_FP_MUL_ADDSQR1:
     case KZGPOT_FP_MUL_ADDSQR8: return 3;
     case KZGPOT_FP_MUL:
     case KZGPOT_FP_EQ:
@@ -135,8 +134,7 @@ __global__ void __launch_bounds__(kBlock) k_fp_op(long n, const uint32_t* __rest
       if constexpr (OP == KZGPOT_FP_SQR) fp_sqr(o, x[0]);
       if constexpr (OP == KZGPOT_FP_MUL_SUM2) fp_mul_sum2(o, x[0], x[1], x[2], x[3]);
       if constexpr (OP == KZGPOT_FP_MUL_SUM3) fp_mul_sum3(o, x[0], x[1], x[2], x[3], x[4], x[5]);
-      if constexpr (OP == KZGPOT_FP_MUL_ADDSQR1) fp_mul_addsqr<1>(o, x[0], x[1], x[2]);
-      if constexpr (OP == KZGPOT_FP_MUL_ADDSQR8) fp_mul_addsqr<8>(o, x[0], x[1], x[2]);
+      if constexpr (OP == KZGPOT_FP_MUL_ADDSQR8) fp_mul_add8sqr(o, x[0], x[1], x[2]);
       if constexpr (OP == KZGPOT_FP_NORM) fp_norm(o, x[0]);
       if constexpr (OP == KZGPOT_FP_HALF) fp_half(o, x[0]);
       if constexpr (OP == KZGPOT_FP_REDUCE_ONCE) fp_reduce_once(o, x[0]);
@@ -208,7 +206,6 @@ extern "C" int kzgpot_test_fp_op(int op, int field, long n, const uint32_t* a, c
     KZG_BOTH(KZGPOT_FP_SQR)
     KZG_BLS(KZGPOT_FP_MUL_SUM2)
     KZG_BLS(KZGPOT_FP_MUL_SUM3)
-    KZG_BLS(KZGPOT_FP_MUL_ADDSQR1)
     KZG_BLS(KZGPOT_FP_MUL_ADDSQR8)
     KZG_BLS(KZGPOT_FP_NORM)
     KZG_BLS(KZGPOT_FP_HALF)

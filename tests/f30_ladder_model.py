@@ -15,29 +15,16 @@ B = (d, top, v): |lower digit| <= d, |top digit| <= top, |value| <= v. Every fun
 So one bounds-only run of a formula proves it for every input inside its input bounds, and the
 exact runs check the bound derivations and the arithmetic. tests/test_f30_ladder.py drives both.
 """
-import os
-import re
+import field_bounds_model
 
-P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
-HERE = os.path.dirname(os.path.abspath(__file__))
-HDR = os.path.join(HERE, "..", "kzg-setup-powersoftau_amd", "csrc", "bls12_381_consts.hpp")
+P = field_bounds_model.FIELDS["bls12_381"][0]
+HDR = field_bounds_model.load_consts()  # bls12_381_consts.hpp, by name
 N = 13
 M30 = (1 << 30) - 1
 R30 = 1 << 390
-ABS_U = 0xD201000000010000
+ABS_U = HDR["BLS_ABS_U"]
 ZK = 16  # curve.hpp F30_ZK
-
-
-def _consts():
-    text = open(HDR).read()
-    s32 = {n: [int(v) for v in b.split(",")]
-           for n, b in re.findall(r"static constexpr int32_t (\w+)\[\d+\] = \{([^}]*)\}", text)}
-    pinv = int(re.search(r"PINV30 = 0x([0-9a-f]+)u", text).group(1), 16)
-    return s32, pinv
-
-
-S32, PINV30 = _consts()
-P30 = S32["P30"]
+P30, PINV30 = HDR["P30"], HDR["PINV30"]
 LOW = sum(1 << (30 * k) for k in range(N - 1))  # value of the lower digits, all 1
 
 
@@ -141,7 +128,9 @@ def _check_columns(pairs, what):
 
 def _scan(prods, sqrs):
     """The device column scan on exact digits: prods = [(a, b), ...] full products, sqrs = [c, ...]
-    squares computed as cross products once (c_j * 2 c_k) plus the diagonal."""
+    squares computed as cross products once (c_j * 2 c_k) plus the diagonal. A lower column's a_i b_0
+    is the last product INSIDE the column's run, before the m p products, as in the device's serial
+    run (f30_mul puts it at x[n] of the one statement); tests/test_fp30.py drives this scan too."""
     m = [0] * N
     r = [0] * N
     acc = 0
@@ -359,7 +348,7 @@ def in_subgroup_fast_g1(x, w):
     q1 = mul_abs_u_affine(x, w)
     X, W, Z = mul_abs_u_affine(q1[0], q1[1])
     Z = mul(Z, q1[2])
-    return jac_eq_affine(X, W, Z, mul(x, of_int(val(S32["BETA30"]))), neg(w))
+    return jac_eq_affine(X, W, Z, mul(x, of_int(val(HDR["BETA30"]))), neg(w))
 
 
 # ------------------------------------------------------------------------------- 14 x 28 <-> 13 x 30

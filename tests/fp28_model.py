@@ -2,8 +2,8 @@
 both fields (p, NL, LB from field_bounds_model.FIELDS; the constants read from the .hpp files, -p^-1
 derived and compared with the header's).
 
-  * scan(): the column scan of the six multiply forms (fp_mul, fp_sqr, fp_mul_sum2, fp_mul_sum3,
-    fp_mul_addsqr<1|8>) with the device's accumulators — acc, acc2, acc3 and accp — each checked
+  * scan(): the column scan of the five multiply forms (fp_mul, fp_sqr, fp_mul_sum2, fp_mul_sum3,
+    fp_mul_add8sqr) with the device's accumulators — acc, acc2, acc3 and accp — each checked
     against uint64 at every step, every doubled or scaled limb against uint32, and the carry out of
     the last column against zero (the result would not fit NL limbs). The interval proof of
     tests/field_bounds_model.py bounds the column SUMS; this follows the chains the device keeps.
@@ -52,7 +52,7 @@ class Field:
         self.PINV = (-pow(self.p, -1, 1 << self.LB)) % (1 << self.LB)
         path = os.path.join(CSRC, hdr)
         text = open(path).read().split("\n};")[0]  # the traits struct
-        self.C = M._load_consts(path)
+        self.C = M.load_consts(path)
         self.NW = int(re.search(r"int NW = (\d+);", text).group(1))
         self.INV_RHO = float(re.search(r"INV_RHO = ([0-9.e+-]+);", text).group(1))
         # a borrowed constant's comment: "<m> p, limbs >= 2^<x> - 2^<y>, dominates values < <v> p"
@@ -91,7 +91,7 @@ def scan(F, prods, sq=None, scale=1, sq_in_acc=False, bits=64, doubling=True, st
     """(sum of a b over prods [+ scale sq^2]) R^-1 mod p as the device scans it: the first product's
     chain runs on acc (on top of the incoming carry), the second and third on acc2 and acc3, m p on
     accp; a square is cross products once, sq_j (2 scale sq_k), plus the diagonal sq_j (scale sq_j), on
-    acc2 (fp_mul_addsqr) or on acc (fp_sqr: sq_in_acc). bits = 64 raises OverflowError when an
+    acc2 (fp_mul_add8sqr) or on acc (fp_sqr: sq_in_acc). bits = 64 raises OverflowError when an
     accumulator leaves uint64; a smaller bits WRAPS instead (the wrong device a test must tell apart).
     stats["peak"]: the largest accumulator value seen."""
     N, LB, MASK, PL = F.NL, F.LB, F.MASK, F.PL
@@ -162,9 +162,8 @@ def mul_sum3(F, a, b, c, d, e, f, **kw):
     return scan(F, [(a, b), (c, d), (e, f)], **kw)
 
 
-def mul_addsqr(F, a, b, c, scale=8, **kw):
-    assert scale in (1, 8)
-    return scan(F, [(a, b)], sq=c, scale=scale, **kw)
+def mul_add8sqr(F, a, b, c, **kw):
+    return scan(F, [(a, b)], sq=c, scale=8, **kw)
 
 
 # ------------------------------------------------------------------------------- limb-wise forms

@@ -28,8 +28,7 @@ extern "C" {
 #define KZGPOT_FP_SQR 1          /* a^2 R^-1 */
 #define KZGPOT_FP_MUL_SUM2 2     /* (a b + c d) R^-1 */
 #define KZGPOT_FP_MUL_SUM3 3     /* (a b + c d + e f) R^-1 */
-#define KZGPOT_FP_MUL_ADDSQR1 4  /* fp_mul_addsqr<1>: (a b + c^2) R^-1 */
-#define KZGPOT_FP_MUL_ADDSQR8 5  /* fp_mul_addsqr<8>: (a b + 8 c^2) R^-1 */
+#define KZGPOT_FP_MUL_ADDSQR8 5  /* fp_mul_add8sqr: (a b + 8 c^2) R^-1; 4 is not used */
 #define KZGPOT_FP_NORM 6
 #define KZGPOT_FP_HALF 7
 #define KZGPOT_FP_REDUCE_ONCE 8

@@ -162,16 +162,16 @@ def test_bound_set_closed_under_a_ladder_step():
     #                                                        branch loads (base, 1): inside, above)
     # the closing multiply and the comparison of in_subgroup_fast_g1, from any state in the set
     z = M.mul(s[2], s[2])
-    xb = M.mul(M.bound_only(M.of_int(P - 1).b), M.of_int(val(M.S32["BETA30"])))
+    xb = M.mul(M.bound_only(M.of_int(P - 1).b), M.of_int(val(M.HDR["BETA30"])))
     M.jac_eq_affine(s[0], s[1], z, xb, M.neg(base))
 
 
 def test_constants():
-    assert val(M.S32["ONE30"]) == R30 % P
-    beta = val(M.S32["BETA30"]) * pow(R30, -1, P) % P
+    assert val(M.HDR["ONE30"]) == R30 % P
+    beta = val(M.HDR["BETA30"]) * pow(R30, -1, P) % P
     assert beta != 1 and pow(beta, 3, P) == 1
     for name in ("ONE30", "BETA30"):
-        assert all(-(1 << 29) <= d < (1 << 29) for d in M.S32[name][:-1])
+        assert all(-(1 << 29) <= d < (1 << 29) for d in M.HDR[name][:-1])
 
 
 # ------------------------------------------------------------------------------- 3. algebra

@@ -14,34 +14,13 @@ import field_bounds_model as M
 
 
 def test_ladders_closed():
-    """G1 ladders (the G2 ones: test_g2_lazy_ladder_closed)."""
-    two = False
-    F = M.Field(two)
+    """The radix-2^28 G1 ladder (in_subgroup_ref<fp>; the group FFT's and the MSM's double-and-add):
+    jac_dbl + jac_madd of a normalized base, then jac_eq_affine. Every jac_madd<fp> call site hands it
+    a normalized base. (The G1 fast ladders run on radix 2^30: test_f30_ladder.py; the G2 ladders:
+    test_g2_lazy_ladder_closed, test_g2_fast_ladder_w_closed.)"""
     base = M.normalized(Fraction(101, 100))
-    S1 = M.ladder_invariant(F, base, base)                     # mul_abs_u_affine / in_subgroup_ref
-    if not two:
-        # G1 second ladder: Q1 = S1's (X, Y) is the affine base on the isomorphic curve; the
-        # result's Z is multiplied by Q1's Z before the comparison (curve.hpp in_subgroup_fast_g1)
-        S2 = M.ladder_invariant(F, S1[0], S1[1])
-        z = M.mul(S2[2], S1[2], "Z'Z")
-        beta_x = M.mul(base, M.normalized(1))
-        ny = M.norm(M.subk(M.normalized(0), base, "KB_64_31"))
-        M.jac_eq_affine(F, S2[0], S2[1], z, beta_x, ny)
-    M.jac_eq_affine(F, *S1, base, base)
-
-
-def test_g1_fast_ladders_w_closed():
-    """The G1 fast ladders (curve.hpp in_subgroup_fast_g1: jac_tpl_affine_w / jac_dbl_w /
-    jac_madd_w, W = 2Y): the base's w = 2y (a doubled normalized y), the second ladder's base is
-    Q1 = (X, W) of the first, and the comparison is with (beta x, 2 (-y))."""
-    base = M.normalized(Fraction(101, 100))
-    w = M.shl(base, 1, "2y")
-    S1 = M.ladder_invariant_w(base, w)
-    S2 = M.ladder_invariant_w(S1[0], S1[1])
-    z = M.mul(S2[2], S1[2], "Z'Z")
-    beta_x = M.mul(base, M.normalized(1))
-    nw = M.shl(M.norm(M.subk(M.normalized(0), base, "KB_64_31")), 1, "-2y")
-    M.jac_eq_affine(M.Field(False), S2[0], S2[1], z, beta_x, nw)
+    S1 = M.ladder_invariant(base, base)
+    M.jac_eq_affine(*S1, base, base)
 
 
 def _pow_pm3d4(a):
@@ -54,10 +33,10 @@ def _pow_pm3d4(a):
     a2 = M.sqr(a, "a^2")
     t = M.mul(a, a2, "tab")
     for _ in range(8):
-        t = M.vmax(t, M.mul(t, a2, "tab"))
+        t = M.join(t, M.mul(t, a2, "tab"))
     acc = t
     for _ in range(460):
-        acc = M.vmax(M.sqr(acc, "sq"), M.mul(acc, t, "mul"))
+        acc = M.join(M.sqr(acc, "sq"), M.mul(acc, t, "mul"))
     return acc
 
 
@@ -87,13 +66,13 @@ def test_fp2_sqrt_and_psi():
     gam = M.mul(_pow_pm3d4(nrm), nrm, "gam")
     M.canon_ok(M.subk(M.mul(gam, gam), nrm, "KB_64_31"), "gam^2 == N")
     d = M.half(M.norm(M.add_nr(a.c0, gam)), "d")  # fp_half((a0 + gam) normalized)
-    d = M.vmax(d, a.c0)
+    d = M.join(d, a.c0)
     t = _pow_pm3d4(d)
     s = M.mul(t, d, "s")
     M.canon_ok(M.subk(M.mul(s, s), d, "KB_64_31"), "s^2 == d")
     h = M.mul(M.half(a.c1, "a1/2"), t, "h")
     nh = M.sub_red(M.normalized(0), h, "-h")
-    y = M.V2(M.vmax(s, nh), M.vmax(h, s))
+    y = M.V2(M.join(s, nh), M.join(h, s))
     for c in (y.c0, y.c1):
         M.from_mont_ok(c)
         M.reduce_once_ok(c, "k_g2_codec: the ladder's Montgomery y")
@@ -108,19 +87,19 @@ def test_fp2_sqrt_and_psi():
     py = M.V2(pm.c0, M.sub_red(M.normalized(0), pm.c1))
     py = M.f2_mul(py, M.V2(M.normalized(1), M.normalized(1)))
     py = M.V2(M.sub_red(M.normalized(0), py.c0), M.sub_red(M.normalized(0), py.c1))
-    S1 = M.ladder_invariant_fp2_lz(pm, pm)
-    M.jac_eq_affine_fp2_lz(*S1, px, py)
+    S1 = M.ladder_invariant_fp2(pm, pm)
+    M.jac_eq_affine_fp2(*S1, px, py)
 
 
 def test_g2_lazy_ladder_closed():
     """G2 ladders (mul_abs_u_affine / in_subgroup_ref over Fp2) in the carry-free discipline:
     curve.hpp jac_dbl(jac<fp2>&) / jac_madd(jac<fp2>&, ..) / jac_eq_affine(jac<fp2>, ..)."""
     base = M.V2(M.normalized(Fraction(101, 100)), M.normalized(Fraction(101, 100)))
-    S = M.ladder_invariant_fp2_lz(base, base)
-    M.jac_eq_affine_fp2_lz(*S, base, base)
+    S = M.ladder_invariant_fp2(base, base)
+    M.jac_eq_affine_fp2(*S, base, base)
     # psi(P) and -y are reduced (< 2p) values from the generic Fp2 helpers: within the same bound
     red = M.V2(M.reduced(), M.reduced())
-    M.jac_eq_affine_fp2_lz(*S, red, red)
+    M.jac_eq_affine_fp2(*S, red, red)
 
 
 def test_g2_fast_ladder_w_closed():
@@ -128,24 +107,17 @@ def test_g2_fast_ladder_w_closed():
     (x', 2 y') for psi's output (x', y') reduced."""
     base = M.V2(M.normalized(Fraction(101, 100)), M.normalized(Fraction(101, 100)))
     w = M.V2(M.shl(base.c0, 1), M.shl(base.c1, 1))
-    S = M.ladder_invariant_fp2_w(base, w)
+    S = M.ladder_invariant_fp2(base, w, w=True)
     red = M.V2(M.reduced(), M.reduced())
-    M.jac_eq_affine_fp2_lz(*S, red, M.V2(M.shl(red.c0, 1), M.shl(red.c1, 1)))
+    M.jac_eq_affine_fp2(*S, red, M.V2(M.shl(red.c0, 1), M.shl(red.c1, 1)))
 
 
 def test_g2_synth_madd_chain_lazy():
     """k_synth<fp2> (synth_kernels.hip): back-to-back lazy Fp2 mixed additions of table points,
     then to_affine's reduced-discipline inverse and multiplies (inputs normalized, any value)."""
     base = M.V2(M.normalized(Fraction(101, 100)), M.normalized(Fraction(101, 100)))
-    S = (base, base, M.V2(M.normalized(1), M.normalized(0)))
-    for _ in range(40):
-        T = M.jac_madd_fp2_lz(*S, base, base)
-        T = tuple(M.V2(M.vmax(a.c0, b.c0), M.vmax(a.c1, b.c1)) for a, b in zip(S, T))
-        if all(M._within(M.Field(True), a, b) for a, b in zip(T, S)):
-            break
-        S = tuple(M.V2(M._inflate1(t.c0, 1.01), M._inflate1(t.c1, 1.01)) for t in T)
-    else:
-        raise AssertionError("lazy fp2 madd chain bound set not closed")
+    start = (base, base, M.V2(M.normalized(1), M.normalized(0)))
+    S = M.closed_set(start, lambda *S: M.jac_madd_fp2(*S, base, base), rounds=0)
     X, Y, Z = S
     for c in (X.c0, X.c1, Y.c0, Y.c1):  # f_mul(x, p.x, z2) with z2 reduced: a mul_sum2 on normalized limbs
         M.reduce_once_ok(M.mul_sum2(c, M.reduced(), c, M.subk(M.normalized(0), M.reduced(), "KB_4_28")))
@@ -164,17 +136,8 @@ def test_bounds_model_catches_overflow():
 def test_synth_madd_chain():
     """k_synth (synth_kernels.hip): 31 back-to-back mixed additions of table points (no doubling
     in between), then to_affine. Bound set closed under madd alone."""
-    F = M.Field(False)
     base = M.normalized(Fraction(101, 100))
-    S = (base, base, M.normalized(1))
-    for _ in range(40):
-        T = M.jac_madd(F, *S, base, base)
-        T = tuple(M.join(F, a, b) for a, b in zip(S, T))
-        if all(M._within(F, a, b) for a, b in zip(T, S)):
-            break
-        S = tuple(M._inflate(F, t) for t in T)
-    else:
-        raise AssertionError("madd chain bound set not closed")
+    S = M.closed_set((base, base, M.normalized(1)), lambda *S: M.jac_madd(*S, base, base), rounds=0)
     X, Y, Z = S
     zi = _pow_pm3d4(Z)
     zi = M.mul(M.mul(M.mul(zi, zi), zi), Z, "inv")

@@ -73,16 +73,15 @@ def canon_jac_to_affine_fp(X, Y, Z):
 
 
 def test_g1_butterfly_bounds():
-    F = M.Field(False)
     base = M.normalized(Fraction(101, 100))  # the work buffer holds canonical values: a subset
-    S = M.ladder_invariant(F, base, base)
-    M.jac_eq_affine(F, *S, base, base)  # the set test_field_bounds.py proves
+    S = M.ladder_invariant(base, base)
+    M.jac_eq_affine(*S, base, base)  # the set test_field_bounds.py proves
     for v in S:  # T itself is canonicalised when P is infinite, and in the scale / per-point pass
         canon(v, "T")
     canon_jac_to_affine_fp(canonical("T.X"), canonical("T.Y"), canonical("T.Z"))  # k_fft_point_mul
     ny = neg_canon(canonical("P.y"))
     for py in (canonical("P.y"), ny):  # R0 = T + P, R1 = T + (-P), from any ladder state
-        R = M.jac_madd(F, *S, canonical("P.x"), py)
+        R = M.jac_madd(*S, canonical("P.x"), py)
         X, Y, Z = (canon(v, "R") for v in R)
     # one inversion for both results
     z0, z1 = canonical("Z0"), canonical("Z1")
@@ -100,10 +99,9 @@ def test_g1_load_and_h_bases_bounds():
     """k_fft_load: a range-checked coordinate (< p) to Montgomery form and one conditional
     subtraction. k_h_bases: (x, y, 1) + (x', -y') from records of a checked decode, then the
     single-point inversion."""
-    F = M.Field(False)
     xm = M.mul(canonical("x"), canonical("R2"), "to_mont")
     reduce_once(xm, "load")
-    R = M.jac_madd(F, xm, xm, M.normalized(1), xm, neg_canon(reduce_once(xm)))
+    R = M.jac_madd(xm, xm, M.normalized(1), xm, neg_canon(reduce_once(xm)))
     canon_jac_to_affine_fp(*(canon(v, "h") for v in R))
 
 
@@ -144,8 +142,8 @@ def canon_jac_to_affine_fp2(X, Y, Z):
 
 def test_g2_butterfly_bounds():
     base = _v2(M.normalized(Fraction(101, 100)))
-    S = M.ladder_invariant_fp2_lz(base, base)
-    M.jac_eq_affine_fp2_lz(*S, base, base)
+    S = M.ladder_invariant_fp2(base, base)
+    M.jac_eq_affine_fp2(*S, base, base)
     for v in S:
         canon(v.c0, "T.c0"), canon(v.c1, "T.c1")
     T = _v2(canonical("T"))
@@ -153,7 +151,7 @@ def test_g2_butterfly_bounds():
     P = _v2(canonical("P"))
     nP = M.V2(neg_canon(P.c0), neg_canon(P.c1))
     for py in (P, nP):
-        R = M.jac_madd_fp2_lz(*S, P, py)
+        R = M.jac_madd_fp2(*S, P, py)
         for v in R:
             canon(v.c0, "R.c0"), canon(v.c1, "R.c1")
     # the tail runs on canonical values in the reduced Fp2 discipline (f_mul / f_sqr / f_inv)

@@ -23,16 +23,15 @@ def zero():
 
 
 def test_g1_chained_addition_link():
-    F = M.Field(False)
     base = canonical("base")
     for Z in (canonical("Z"), zero()):
         acc = (canonical("X"), canonical("Y"), Z)
-        for v in M.jac_madd(F, *acc, base, base):
+        for v in M.jac_madd(*acc, base, base):
             canon(v, "madd")
-        for v in M.jac_dbl(F, *acc):
+        for v in M.jac_dbl(*acc):
             canon(v, "dbl")
     # empty sum: X = Y = Z = 0
-    for v in M.jac_madd(F, zero(), zero(), zero(), base, base):
+    for v in M.jac_madd(zero(), zero(), zero(), base, base):
         canon(v, "madd from the empty sum")
 
 
@@ -40,11 +39,11 @@ def test_g2_chained_addition_link():
     base = _v2(canonical("base"))
     for Z in (_v2(canonical("Z")), _v2(zero())):
         acc = (_v2(canonical("X")), _v2(canonical("Y")), Z)
-        for v in M.jac_madd_fp2_lz(*acc, base, base):
+        for v in M.jac_madd_fp2(*acc, base, base):
             canon(v.c0, "madd.c0"), canon(v.c1, "madd.c1")
-        for v in M.jac_dbl_fp2_lz(*acc):
+        for v in M.jac_dbl_fp2(*acc):
             canon(v.c0, "dbl.c0"), canon(v.c1, "dbl.c1")
-    for v in M.jac_madd_fp2_lz(_v2(zero()), _v2(zero()), _v2(zero()), base, base):
+    for v in M.jac_madd_fp2(_v2(zero()), _v2(zero()), _v2(zero()), base, base):
         canon(v.c0, "madd.c0"), canon(v.c1, "madd.c1")
 
 
@@ -59,13 +58,12 @@ def test_g2_normalisation():
 
 
 def test_final_ladder_is_the_proven_set():
-    F = M.Field(False)
     base = canonical("T_k")
-    S = M.ladder_invariant(F, base, base)
+    S = M.ladder_invariant(base, base)
     for v in S:
         canon(v, "final")
     base2 = _v2(canonical("T_k"))
-    for v in M.ladder_invariant_fp2_lz(base2, base2):
+    for v in M.ladder_invariant_fp2(base2, base2):
         canon(v.c0, "final.c0"), canon(v.c1, "final.c1")
     # the ladder starts from X = Y = Z = 0, below every bound of S
     assert all(z <= s for v in S for z, s in zip(zero().limbs, v.limbs))

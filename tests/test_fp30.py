@@ -7,139 +7,37 @@ fp_pow_pm3d4_30: BLS12-381's square-root exponentiation), CPU only.
 2. An exact model: the device functions step by step on Python integers, with every 64-bit
    accumulator checked against the int64 range, against plain modular arithmetic — the
    exponentiation (same schedule as the header) on random and edge inputs, and the conversions.
+The column scan, the conversions and the header constants are those of tests/f30_ladder_model.py
+(through tests/fp28_model.py where the loose-limb fp_norm step comes first): one model of the core.
 """
-import os
 import random
-import re
 
 import pytest
 
-P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
-HERE = os.path.dirname(os.path.abspath(__file__))
-HDR = os.path.join(HERE, "..", "kzg-setup-powersoftau_amd", "csrc", "bls12_381_consts.hpp")
-N = 13
-M30 = (1 << 30) - 1
-R30 = 1 << 390
+import f30_ladder_model as L
+import fp28_model as F28
+from f30_ladder_model import N, P, P30, PINV30, R30, val
+
 R28 = 1 << 392
 E = (P - 3) // 4
 TOP_IN = (1 << 23) + 1  # |top digit| < TOP_IN for every f30 operand (see test_top_digit_bounds)
-
-
-def _consts():
-    text = open(HDR).read()
-    s32 = {n: [int(v) for v in b.split(",")]
-           for n, b in re.findall(r"static constexpr int32_t (\w+)\[\d+\] = \{([^}]*)\}", text)}
-    pinv = int(re.search(r"PINV30 = 0x([0-9a-f]+)u", text).group(1), 16)
-    steps_sq = [int(v) for v in re.search(r"SQRT_STEP_SQ\[SQRT_STEPS\] = \{([^}]*)\}", text).group(1).split(",")]
-    steps_idx = [int(v) for v in re.search(r"SQRT_STEP_IDX\[SQRT_STEPS\] = \{([^}]*)\}", text).group(1).split(",")]
-    table = [int(v) for v in re.search(r"SQRT_TABLE_EXP\[SQRT_TABLE\] = \{([^}]*)\}", text).group(1).split(",")]
-    return s32["P30"], pinv, s32["POW30_OUT"], steps_sq, steps_idx, table
-
-
-P30, PINV30, POW30_OUT, STEP_SQ, STEP_IDX, TABLE_EXP = _consts()
-
-
-def val(d):
-    return sum(v << (30 * k) for k, v in enumerate(d))
-
-
-def s64(x, what):
-    if not -(1 << 63) <= x < (1 << 63):
-        raise OverflowError(f"{what}: {x:#x} leaves int64")
-    return x
-
-
-def sext30(x):
-    x &= M30
-    return x - (1 << 30) if x >= 1 << 29 else x
+POW30_OUT, STEP_SQ, STEP_IDX, TABLE_EXP = (L.HDR[k] for k in ("POW30_OUT", "SQRT_STEP_SQ", "SQRT_STEP_IDX", "SQRT_TABLE_EXP"))
 
 
 def f30_mul(a, b, sq=False):
-    """fp381.hpp f30_mul / f30_sqr, column by column (the compiler may re-associate the sums of
-    one column; every partial sum is bounded by the sum of absolute values checked in
-    test_worst_case_columns)."""
-    m = [0] * N
-    r = [0] * N
-    acc = 0
-    for i in range(2 * N - 1):
-        j0 = 0 if i < N else i - (N - 1)
-        j1 = i - 1 if i < N else N - 1
-        accab = 0 if i < N else 1 << 29
-        if sq:
-            d = [2 * x for x in a]
-            for j in range(j0, i):
-                if 2 * j < i:
-                    accab = s64(accab + a[j] * d[i - j], "ab")
-            if i % 2 == 0:
-                accab = s64(accab + a[i // 2] * a[i // 2], "ab")
-        else:
-            for j in range(j0, j1 + 1):
-                accab = s64(accab + a[j] * b[i - j], "ab")
-        accp = 0
-        for j in range(j0, j1 + 1):
-            accp = s64(accp + m[j] * P30[i - j], "mp")
-        acc = s64(acc + accab, "acc")
-        if i < N:
-            if not sq:
-                acc = s64(acc + a[i] * b[0], "acc")
-            acc = s64(acc + accp, "acc")
-            m[i] = sext30((acc & 0xFFFFFFFF) * PINV30)
-            acc = s64(acc + m[i] * P30[0], "acc")
-            assert acc % (1 << 30) == 0
-        else:
-            acc = s64(acc + accp, "acc")
-            r[i - N] = (acc & M30) - (1 << 29)
-        acc >>= 30
-    r[N - 1] = acc
-    return r
+    """fp381.hpp f30_mul / f30_sqr: the ladder model's column scan, every accumulator checked against
+    int64 (the compiler may re-associate the sums of one column; every partial sum is bounded by the
+    sum of absolute values checked in test_worst_case_columns)."""
+    return L._scan([], [a]) if sq else L._scan([(a, b)], [])
 
 
 def f30_from_fp(limbs28):
     """fp_norm (carry to 28-bit limbs, top keeps the excess), then 30-bit digits, balanced."""
-    n, c = [], 0
-    for k in range(13):
-        t = limbs28[k] + c
-        n.append(t & ((1 << 28) - 1))
-        c = t >> 28
-    n.append(limbs28[13] + c)
-    assert all(x < 1 << 32 for x in n)
-    r, c = [], 0
-    for k in range(N):
-        bit = 30 * k
-        i, off = bit // 28, bit % 28
-        u = (n[i] >> off) | ((n[i + 1] << (28 - off)) & 0xFFFFFFFF if i + 1 < 14 else 0)
-        u &= 0xFFFFFFFF
-        if k < N - 1:
-            t = (u & M30) + c
-            c = (t + (1 << 29)) >> 30
-            r.append(sext30(t))
-        else:
-            r.append(u + c)
-    return r
+    return F28.f30_from_fp(limbs28)
 
 
 def fp_from_f30(z):
-    u, c = [], 0
-    for k in range(N):
-        t = z[k] + P30[k] + c
-        assert -(1 << 31) <= t < (1 << 31)
-        if k < N - 1:
-            u.append(t & M30)
-            c = t >> 30
-        else:
-            assert t >= 0
-            u.append(t)
-    limbs = []
-    for j in range(14):
-        bit = 28 * j
-        i, off = bit // 30, bit % 30
-        v = u[i] >> off
-        if off > 2 and i + 1 < N:
-            v |= (u[i + 1] << (30 - off)) & 0xFFFFFFFF
-        limbs.append(v & ((1 << 28) - 1) if j < 13 else v)
-    x = sum(l << (28 * j) for j, l in enumerate(limbs))
-    assert x < 2 * P
-    return x - P if x >= P else x
+    return L.val28(L.fp_from_f30(z))
 
 
 def pow_pm3d4_30(limbs28):
@@ -174,7 +72,7 @@ def pow_pm3d4_30(limbs28):
 def limbs28(x, loose=False, rng=None):
     """x as 14 limbs of 28 bits; loose: push random multiples of 2^28 down into lower limbs
     (limbs up to 2^30, same value), as the kernels' lazy sums produce."""
-    lim = [(x >> (28 * k)) & ((1 << 28) - 1) for k in range(13)] + [x >> 364]
+    lim = L.limbs28(x)
     if loose:
         for k in range(13, 0, -1):
             take = min(lim[k], rng.randrange(4))
@@ -250,13 +148,7 @@ def test_conversions_exact():
         a = f30_from_fp(limbs28(x, loose=bool(t & 1), rng=rng))
         assert val(a) == x and all(-(1 << 29) <= d < (1 << 29) for d in a[:-1]) and abs(a[-1]) < TOP_IN
         z = rng.randrange(-(P - 1), P) if t >= 6 else [0, 1, -1, P - 1, -(P - 1), P // 2][t]
-        zd, rest = [], z
-        for k in range(N - 1):
-            d = sext30(rest)
-            zd.append(d)
-            rest = (rest - d) >> 30
-        zd.append(rest)
-        assert fp_from_f30(zd) == z % P
+        assert fp_from_f30(L.digits(z)) == z % P
 
 
 def test_pow_exact():

@@ -12,8 +12,8 @@ slip names its own slot (j, k):
   * f30_mul_addsqr: the f30_mul cases with c = 0 (the product alone) and the f30_sqr cases as c with
     a = b = 0 (the squared operand alone).
 
-Expected digits: the column-scan models of test_gpu_f30_core.py (tests/test_fp30.py,
-tests/f30_ladder_model.py) on Python integers, which raise where an int64 accumulator or an int32
+Expected digits: the column-scan model of test_gpu_f30_core.py (tests/f30_ladder_model.py) on
+Python integers, which raises where an int64 accumulator or an int32
 digit would overflow, so every operand is also proven to be inside the device functions' range.
 Launches: the hook of test_gpu_f30_core.py (libkzgpot_test.so kzgpot_test_f30_op), 256 lanes (one
 block) and 320 lanes (a partial last block) at a time."""

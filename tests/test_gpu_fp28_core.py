@@ -1,6 +1,6 @@
 """The 14 x 28 / 9 x 29 limb core of csrc/fp381.hpp on the GPU, one function per lane on supplied limbs
 (libkzgpot_test.so kzgpot_test_fp_op, csrc/fp_hooks.hip; tests/kzgpot_test_fp_hooks.h), against the exact
-integer model tests/fp28_model.py LIMB FOR LIMB: the six multiply forms, the reductions and comparisons,
+integer model tests/fp28_model.py LIMB FOR LIMB: the five multiply forms, the reductions and comparisons,
 fp_is_zero / fp_eq / f30_is_zero<F30_ZK>, every borrowed-constant form fp_subk_nr<K> / fp_negk_nr<K>, the
 word and Montgomery conversions, the Fp2 f_mul / f_sqr and the 14 x 28 <-> 13 x 30 conversions, for
 BLS12-381 and, where bn254_kernels.hip uses a function, BN254. The codec tests see canonical bytes only:
@@ -21,7 +21,7 @@ Multiply forms, per form:
     test_field_bounds_lagrange.py, and the BN254 chain), EVERY LIMB AT ITS BOUND; none is left out;
   * limb-bit classes at the limit: fp_mul's documented limb-bit sums of 60 (28 + 32 with limbs up to
     2^32 - 17, 29 + 31, 30 + 30, both orders); the k-product forms at the sums for which k 14 2^s + 14 2^56
-    stays below 2^64 (59 for fp_mul_sum2 and fp_mul_addsqr, 58 for fp_mul_sum3); fp_sqr at 30 bits, and
+    stays below 2^64 (59 for fp_mul_sum2 and fp_mul_add8sqr, 58 for fp_mul_sum3); fp_sqr at 30 bits, and
     with one limb at 2^31 - 1 (its doubling's edge; all limbs there leave uint64, as the model confirms in
     test_sqr_limit). Lower limbs at the class maximum, the top limbs the largest for which the model's
     result still fits (a search on the CPU model);
@@ -67,8 +67,7 @@ OPS = {
     "fp_sqr": (1, 1, BOTH, "L", "L", F28.sqr),
     "fp_mul_sum2": (2, 4, BLS_ONLY, "L", "L", F28.mul_sum2),
     "fp_mul_sum3": (3, 6, BLS_ONLY, "L", "L", F28.mul_sum3),
-    "fp_mul_addsqr<1>": (4, 3, BLS_ONLY, "L", "L", lambda F, a, b, c, **kw: F28.mul_addsqr(F, a, b, c, 1, **kw)),
-    "fp_mul_addsqr<8>": (5, 3, BLS_ONLY, "L", "L", lambda F, a, b, c, **kw: F28.mul_addsqr(F, a, b, c, 8, **kw)),
+    "fp_mul_addsqr<8>": (5, 3, BLS_ONLY, "L", "L", F28.mul_add8sqr),  # fp_mul_add8sqr, under the id it has had
     "fp_norm": (6, 1, BLS_ONLY, "L", "L", F28.norm),
     "fp_half": (7, 1, BLS_ONLY, "L", "L", F28.half),
     "fp_reduce_once": (8, 1, BLS_ONLY, "L", "L", F28.reduce_once),
@@ -107,7 +106,6 @@ MUL_FORMS = {  # op -> (recorded form, numerator of the residue)
     "fp_sqr": ("sqr", lambda v: v[0] * v[0]),
     "fp_mul_sum2": ("mul_sum2", lambda v: v[0] * v[1] + v[2] * v[3]),
     "fp_mul_sum3": ("mul_sum3", lambda v: v[0] * v[1] + v[2] * v[3] + v[4] * v[5]),
-    "fp_mul_addsqr<1>": ("mul_addsqr", lambda v: v[0] * v[1] + v[2] * v[2]),
     "fp_mul_addsqr<8>": ("mul_add8sqr", lambda v: v[0] * v[1] + 8 * v[2] * v[2]),
 }
 # limb-bit classes per operand (see the module docstring)
@@ -116,7 +114,6 @@ CLASSES = {
     "fp_sqr": [(30,)],
     "fp_mul_sum2": [(x, y, x, y) for x, y in ((28, 31), (31, 28), (29, 30), (30, 29))] + [(28, 31, 31, 28), (29, 30, 30, 29)],
     "fp_mul_sum3": [(x, y) * 3 for x, y in ((28, 30), (30, 28), (29, 29))] + [(28, 30, 30, 28, 29, 29)],
-    "fp_mul_addsqr<1>": [(x, y, 29) for x, y in ((28, 31), (31, 28), (29, 30), (30, 29))],
     "fp_mul_addsqr<8>": [(x, y, 28) for x, y in ((28, 31), (31, 28), (29, 30), (30, 29))],
 }
 
@@ -250,7 +247,7 @@ def class_lanes(F, op):
             t = _largest(lambda t: _accepts(F, op, one(u, t)), u)
             out += [one(u, t), one(u, 0)]
     if op.startswith("fp_mul_addsqr"):  # the squared operand's doubling / scaling edge: 2 S c_k at 32 bits
-        cmax = ((1 << 32) - 1) // (2 * (8 if "8" in op else 1))
+        cmax = ((1 << 32) - 1) // (2 * 8)
         for k in (0, n // 2, n - 2):
             c = [F.MASK] * (n - 1) + [0]
             c[k] = cmax
@@ -693,15 +690,20 @@ def test_operands_inside_the_model(op, field):
 
 
 def test_recorder_yields_every_site():
-    """at least the 909 distinct BLS12-381 operand-bound tuples counted when the recorder was added (396
-    fp_mul sites: a count of 397 includes the deliberate overflow of test_bounds_model_catches_overflow,
-    which is not driven), every one of them a lane with every limb at its bound; the recorder is off and
-    the field restored afterwards"""
+    """at least the 716 distinct BLS12-381 operand-bound tuples of the proofs' entry points, every one of
+    them a lane with every limb at its bound; the recorder is off and the field restored afterwards.
+    The floors are counts of the recorder as it was when it was added (909 tuples: mul 396, mul_sum2 372,
+    sqr 85, mul_sum3 34, mul_add8sqr 13, mul_addsqr 9; a count of 397 fp_mul sites includes the deliberate
+    overflow of test_bounds_model_catches_overflow, which is not driven), taken again on that tree, per
+    entry point, with the two entry points left out that proved ladders no kernel runs and were removed
+    with them: without test_g1_fast_ladders_w_closed (the radix-2^28 W-form G1 ladders) 308 / 363 / 47 /
+    34 / 13 and no mul_addsqr (765); also without the second ladder of test_ladders_closed, whose base
+    was a ladder state, 272 / 361 / 38 / 34 / 11 (716). No tuple that another entry point records left."""
     rec = recorded()
     assert M.RECORD is None and M.NL == 14 and M.P == BLS.p and M.C["P"] == BLS.PL
-    count = {form: len(rec[("bls12_381", form)]) for form in ("mul", "mul_sum2", "sqr", "mul_sum3", "mul_add8sqr", "mul_addsqr")}
-    floor = {"mul": 396, "mul_sum2": 372, "sqr": 85, "mul_sum3": 34, "mul_add8sqr": 13, "mul_addsqr": 9}
-    assert all(count[f] >= floor[f] for f in floor) and sum(count.values()) >= 909, count
+    count = {form: len(rec[("bls12_381", form)]) for form in ("mul", "mul_sum2", "sqr", "mul_sum3", "mul_add8sqr")}
+    floor = {"mul": 272, "mul_sum2": 361, "sqr": 38, "mul_sum3": 34, "mul_add8sqr": 11}
+    assert all(count[f] >= floor[f] for f in floor) and sum(count.values()) >= 716, count
     assert rec[("bn254", "mul")] and rec[("bn254", "sqr")]
     for op, (form, _) in MUL_FORMS.items():
         for field in OPS[op][2]:
@@ -730,7 +732,7 @@ def test_cases_have_teeth(op):
     model = OPS[op][5]
     assert any(model(BLS, *o, bits=63) != w for o, w in zip(ops, want))
     assert all(model(BLS, *o, bits=64) == w for o, w in zip(ops[:50], want))
-    if op in ("fp_sqr", "fp_mul_addsqr<1>", "fp_mul_addsqr<8>"):
+    if op in ("fp_sqr", "fp_mul_addsqr<8>"):
         assert any(model(BLS, *o, doubling=False) != w for o, w in zip(ops, want))
 
 

@@ -1,5 +1,5 @@
 // Chip-wide throughput peak of each Montgomery primitive the codecs use (csrc/fp381.hpp, the
-// product's own functions): fp_mul, fp_sqr, fp_mul_sum2, fp_mul_sum3, fp_mul_addsqr<1> on
+// product's own functions): fp_mul, fp_sqr, fp_mul_sum2, fp_mul_sum3, fp_mul_add8sqr on
 // 14 x 28-bit limbs and f30_mul / f30_sqr on the square root's 13 x 30-bit balanced limbs. Each
 // lane runs CH independent chains of the op on register operands; the launch holds 256 blocks per
 // CU's worth of waves, with LDS padding capping the waves per SIMD (2 = the codecs' occupancy, 4).
@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(256) kpeak(uint32_t* out, const uint32_t* in, 
         if (V == 1) kzgpot::fp_sqr(r, x[c]);
         if (V == 2) kzgpot::fp_mul_sum2(r, x[c], y, x1[c], z);
         if (V == 3) kzgpot::fp_mul_sum3(r, x[c], y, x1[c], z, x2[c], w);
-        if (V == 4) kzgpot::fp_mul_addsqr<1>(r, x[c], y, x1[c]);
+        if (V == 4) kzgpot::fp_mul_add8sqr(r, x[c], y, x1[c]);  // 16 x1_k < 2^32: load_fp's limbs are < 2^28
         if (V >= 3) x2[c] = x1[c];
         if (V >= 2) x1[c] = x[c];
         x[c] = r;
