@@ -110,9 +110,11 @@ hipError_t launch_msm(bool g2, const void* d_bases, const void* d_scalars, uint6
 // poly_workspace_bytes, laid out by poly_plan (plans.hpp).
 hipError_t launch_poly_divide(const void* d_coeffs, uint64_t n, const fr_powers<kPolyPowers>& z_pow, void* d_quotient,
                               void* d_value, uint32_t t, void* d_work, hipStream_t stream);
-// KZG10::open's last step: the two evaluations (64 B at d_values) behind the proof's point, unless
-// the MSM's load rejected a base
-hipError_t launch_open_emit(const void* d_values, void* d_out64, const unsigned long long* d_key, hipStream_t stream);
+// An open's last step: `words` <= 64 words from d_values behind the proof's point, unless the MSM's
+// load rejected a base. KZG10::open emits its two evaluations (16 words), the open from evaluations
+// (evals.hip) its value (8 words).
+hipError_t launch_fr_emit(const void* d_values, void* d_out, uint32_t words, const unsigned long long* d_key,
+                          hipStream_t stream);
 
 // evaluation form (eval_kernels.hip). out[i] = in[i]^-1 mod r, 0 for a zero; n <= kEvalMaxN entries
 // of 32 B (any 256-bit integers in, canonical values out), out may be in; t as for the division.
@@ -122,8 +124,6 @@ hipError_t launch_fr_batch_inverse(const void* d_in, uint64_t n, void* d_out, ui
 // fr_eval_setup's scalars for (p.exp, z), computed on the host (evals.hip). d_work: p.bytes.
 hipError_t launch_evals_divide(const EvalPlan& p, const void* d_evals, const fr_eval_scalars& sc, void* d_quotient,
                                void* d_value, void* d_work, hipStream_t stream);
-// the open's last step: the value (32 B) behind the proof's point, unless the MSM's load rejected a base
-hipError_t launch_evals_emit(const void* d_value, void* d_out32, const unsigned long long* d_key, hipStream_t stream);
 
 // pairing product (pairing_kernels.hip): d_out (576 B of GT, then one u32: 1 if it is one) =
 // prod_{i < k} e(g1[i], g2[i])^KZGPOT_PAIRING_GT_POWER over ark records; k <= kPairMaxK. A malformed

@@ -5,8 +5,9 @@
 // entries, a lane a run of M = S / 256 consecutive ones, staged through LDS as poly_parts.hpp states:
 //   1  lane: the prefix products of its run; the product before entry k stays in registers. A zero
 //      entry counts as 1 and is remembered in a bit mask, so no product is ever zero.
-//   2  block: a prefix scan and a suffix scan over the 256 run products (8 steps each) give lane l
-//      the product E of the runs before it and the product X of the runs behind it.
+//   2  block: a prefix scan and a suffix scan over the 256 run products (8 steps each, written out
+//      in tile_invert, which says why they are not poly_parts.hpp's block_scan) give lane l the
+//      product E of the runs before it and the product X of the runs behind it.
 //   3  lane 255 holds the tile's product and inverts it: the one inversion of the tile, 512 dependent
 //      binary steps (fr_inv_binary, csrc/fr.hpp) in one lane of one wave while the other three wait.
 //   4  E X / (the tile's product) is the inverse of the lane's own run product; the back-sweep over
@@ -72,20 +73,20 @@ __device__ inline void tile_invert(uint4* tile, uint32_t (*rows)[256]) {
   uint32_t zeros = 0;
   auto entry = [&](int k) {
     fr a;
-    tile_get(a, tile, s + 2 * k);
+    get_entry(a, tile, s + 2 * k);
     if (RAW) fr_load(a, a);
     const bool zero = fr_is_zero(a);
     if (zero) {
       zeros |= 1u << k;
       a = fr_one();
     }
-    if (RAW || zero) tile_put(tile, s + 2 * k, a);
+    if (RAW || zero) put_entry(tile, s + 2 * k, a);
     return a;
   };
   auto leave = [&](int k, fr o) {
     if (RAW) fr_store(o, o);
     if ((zeros >> k) & 1) o = fr_zero();
-    tile_put(tile, s + 2 * k, o);
+    put_entry(tile, s + 2 * k, o);
   };
   // the product of the run's entries before each pair (2 p, 2 p + 1); the product before the odd
   // entry is one multiplication away, which halves what the back-sweep needs from registers
@@ -102,6 +103,10 @@ __device__ inline void tile_invert(uint4* tile, uint32_t (*rows)[256]) {
       fr_mul(run, run, entry(2 * p + 1));
     }
   }
+  // The two scans are written out here, not poly_parts.hpp's block_scan: through the shared loop the
+  // batch inversion at the library's tile measured 1 - 2 % slower in two alternating A/B runs (the
+  // scan bodies' mad chains come out in another order; profiles/r14_ab_fr_parts.json), so this
+  // routine keeps the parent's text and, with it, the parent's code.
   // the runs behind this lane's: after step k lane l holds the product of the runs [l, l + 2^(k+1))
   fr acc = run, nb;
   park(rows, tid, acc);
@@ -151,8 +156,8 @@ __device__ inline void tile_invert(uint4* tile, uint32_t (*rows)[256]) {
 #pragma unroll 1
     for (int p = PAIRS - 1; p >= 0; p--) {
       fr a0, a1, o0, o1;
-      tile_get(a0, tile, s + 4 * p);
-      tile_get(a1, tile, s + 4 * p + 2);
+      get_entry(a0, tile, s + 4 * p);
+      get_entry(a1, tile, s + 4 * p + 2);
       const fr b0 = before.get(p);
       fr_mul(o1, b0, a0);  // the product before the odd entry
       fr_mul(o1, o1, inv);
@@ -176,18 +181,6 @@ __device__ inline void stage_out(uint4* out, const uint4* tile, uint64_t blk, ui
     const uint64_t g = base + (uint64_t)i;
     if (g < end) out[g] = tile[i + (i >> (G::LOG2M + 1))];
   }
-}
-
-// x^e from p[k] = x^(2^k), e < 2^kEvalPowers
-__device__ inline fr power_from_table(const fr (&p)[kEvalPowers], uint64_t e) {
-  fr acc = fr_one();
-#pragma unroll 1
-  for (int k = 0; k < kEvalPowers; k++) {
-    fr nx;
-    fr_mul(nx, acc, p[k]);
-    if ((e >> k) & 1) acc = nx;
-  }
-  return acc;
 }
 
 // ---------------------------------------------------------------- batch inversion
@@ -215,7 +208,7 @@ __global__ void __launch_bounds__(256) k_eval_inv(const uint4* __restrict__ eval
   const uint32_t tid = threadIdx.x;
   const uint64_t blk = blockIdx.x, i0 = blk * G::S + (uint64_t)tid * G::M;
   const int s = (int)tid * G::RUN;
-  fr w = power_from_table(sc.pw, i0);
+  fr w = power_from_table<kEvalPowers>(sc.pw, i0, fr_one());
 #pragma unroll 1
   for (int k = 0; k < G::M; k++) {
     const uint64_t i = i0 + (uint64_t)k;
@@ -223,7 +216,7 @@ __global__ void __launch_bounds__(256) k_eval_inv(const uint4* __restrict__ eval
     fr_sub(d, sc.z, w);
     if (i >= n) d = fr_one();  // past the domain (n < S): w^i has wrapped round
     else if (fr_is_zero(d)) *m_word = (uint32_t)i;
-    tile_put(tile, s + 2 * k, d);
+    put_entry(tile, s + 2 * k, d);
     fr_mul(w, w, sc.pw[0]);
   }
   tile_invert<T, false>(tile, rows);
@@ -238,7 +231,7 @@ __global__ void __launch_bounds__(256) k_eval_inv(const uint4* __restrict__ eval
     if (i < n) {
       fr e, v;
       load_entry(e, evals, i);
-      tile_get(v, tile, 2 * j + (j >> G::LOG2M));
+      get_entry(v, tile, 2 * j + (j >> G::LOG2M));
       mul_add(by_inv, e, v, by_inv);
       fr_add(plain, plain, e);
     }
@@ -279,21 +272,19 @@ __global__ void __launch_bounds__(256) k_eval_quot(const uint4* __restrict__ eva
   fr v, w = fr_one(), acc = fr_zero();
   words_in(v, value);
   fr_load(v, v);
-  if (on) w = power_from_table(sc.pw, (blk * G::S + tid + n - m) & (n - 1));  // w^(i - m), i = blk S + tid
+  // w^(i - m), i = blk S + tid
+  if (on) w = power_from_table<kEvalPowers>(sc.pw, (blk * G::S + tid + n - m) & (n - 1), fr_one());
 #pragma unroll 1
   for (int r = 0; r < G::M; r++) {
     const uint64_t i = blk * G::S + (uint64_t)(r * 256) + tid;
     if (i < n) {
-      fr e, q;
+      fr e, vi, q;
       load_entry(e, evals, i);
-      const uint4 lo = inv[2 * i], hi = inv[2 * i + 1];
-      const fr vi = {{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}};
+      get_entry(vi, inv, 2 * i);
       fr_sub(e, v, e);
       fr_mul(q, e, vi);
       if (on) mul_add(acc, q, w, acc);
-      fr_store(q, q);
-      quot[2 * i] = make_uint4(q.v[0], q.v[1], q.v[2], q.v[3]);
-      quot[2 * i + 1] = make_uint4(q.v[4], q.v[5], q.v[6], q.v[7]);
+      store_entry(quot, i, q);
     }
     if (on) fr_mul(w, w, sc.pw[8]);  // 256 entries on
   }
@@ -313,12 +304,6 @@ __global__ void __launch_bounds__(256) k_eval_fix(const uint32_t* __restrict__ q
   fr_sub(acc, fr_zero(), acc);
   fr_store(acc, acc);
   words_out(quot + (uint64_t)m * 8, acc);
-}
-
-__global__ void __launch_bounds__(64) k_eval_emit(const uint32_t* __restrict__ value, uint32_t* __restrict__ out,
-                                                  const unsigned long long* __restrict__ key) {
-  if (*key != ~0ull) return;
-  if (threadIdx.x < 8) out[threadIdx.x] = value[threadIdx.x];
 }
 
 template <int T>
@@ -352,30 +337,14 @@ hipError_t launch_divide(const EvalPlan& p, const void* d_evals, const fr_eval_s
 hipError_t launch_fr_batch_inverse(const void* d_in, uint64_t n, void* d_out, uint32_t t, hipStream_t stream) {
   if (!n) return hipSuccess;
   if (!batch_inverse_tiles(n, t)) return hipErrorInvalidValue;
-  switch (t) {
-    case 8: return launch_inverse<8>(d_in, n, d_out, stream);
-    case 9: return launch_inverse<9>(d_in, n, d_out, stream);
-    case 10: return launch_inverse<10>(d_in, n, d_out, stream);
-    case 11: return launch_inverse<11>(d_in, n, d_out, stream);
-    default: return launch_inverse<12>(d_in, n, d_out, stream);
-  }
+  return with_tile<kPolyTileMin, kPolyTileMax>(t, [&](auto T) { return launch_inverse<T()>(d_in, n, d_out, stream); });
 }
 
 hipError_t launch_evals_divide(const EvalPlan& p, const void* d_evals, const fr_eval_scalars& sc, void* d_quotient,
                                void* d_value, void* d_work, hipStream_t stream) {
   if (!p.bytes) return hipErrorInvalidValue;
-  switch (p.t) {
-    case 8: return launch_divide<8>(p, d_evals, sc, d_quotient, d_value, d_work, stream);
-    case 9: return launch_divide<9>(p, d_evals, sc, d_quotient, d_value, d_work, stream);
-    case 10: return launch_divide<10>(p, d_evals, sc, d_quotient, d_value, d_work, stream);
-    case 11: return launch_divide<11>(p, d_evals, sc, d_quotient, d_value, d_work, stream);
-    default: return launch_divide<12>(p, d_evals, sc, d_quotient, d_value, d_work, stream);
-  }
-}
-
-hipError_t launch_evals_emit(const void* d_value, void* d_out32, const unsigned long long* d_key, hipStream_t stream) {
-  hipLaunchKernelGGL(k_eval_emit, dim3(1), dim3(64), 0, stream, (const uint32_t*)d_value, (uint32_t*)d_out32, d_key);
-  return hipGetLastError();
+  return with_tile<kPolyTileMin, kPolyTileMax>(
+      p.t, [&](auto T) { return launch_divide<T()>(p, d_evals, sc, d_quotient, d_value, d_work, stream); });
 }
 
 }  // namespace kzgpot

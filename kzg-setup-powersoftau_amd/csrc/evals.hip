@@ -79,7 +79,7 @@ int open_evals_dev(const void* d_lagrange, const void* d_evals, uint32_t exp, co
     if ((e = launch_msm(false, d_lagrange, quot, p.ev.n, d_out, flags & KZGPOT_MSM_BASES_MONT,
                         p.c ? p.c : msm_window_bits(p.ev.n), w + p.msm, key, s)))
       return e;
-    return launch_evals_emit(value, (uint8_t*)d_out + kPointBytes, key, s);
+    return launch_fr_emit(value, (uint8_t*)d_out + kPointBytes, 8, key, s);  // the value
   });
 }
 

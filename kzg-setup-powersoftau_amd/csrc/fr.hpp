@@ -2,11 +2,11 @@
 // little-endian words, Montgomery form with R = 2^256, one CIOS multiply. The ABI units start from
 // the host helpers at the end (phase2.hip: the domain root, the powers w^(+-2^k), 1/m; open.hip: the
 // powers z^(2^k)); the kernels use the arithmetic (fft_kernels.hip: k_fft_twiddles builds w^j from
-// those powers; poly_kernels.hip: the polynomial division of KZG10 open; ntt_kernels.hip: the NTT's
-// butterflies, and eval_kernels.hip: the batch inversion and the division in evaluation form, the
-// places where these multiplies are the hot path; evals.hip starts that division from
-// fr_eval_setup). Elsewhere nothing here is hot: ~31 multiplies per twiddle against the 254 point
-// doublings the twiddle then drives.
+// those powers with poly_parts.hpp's ladder; poly_kernels.hip: the polynomial division of KZG10
+// open; ntt_kernels.hip: the NTT's butterflies, and eval_kernels.hip: the batch inversion and the
+// division in evaluation form, the places where these multiplies are the hot path; evals.hip starts
+// that division from fr_eval_setup). Elsewhere nothing here is hot: ~31 multiplies per twiddle
+// against the 254 point doublings the twiddle then drives.
 //
 // Plain C++17 unless the compiler is hipcc, so a host program can include this file alone
 // (tests/host_units/fr_units.cpp and eval_units.cpp, built by g++ with and without sanitizers).
@@ -140,6 +140,7 @@ KZG_HD void fr_store(fr& out, const fr& a) {
 
 // ---------------------------------------------------------------- where the ABI units start from
 // Elements are in Montgomery form; exponents are plain 256-bit integers.
+KZG_HD fr fr_zero() { return fr{{0, 0, 0, 0, 0, 0, 0, 0}}; }
 KZG_HD fr fr_one() {
   fr o;
   for (int i = 0; i < 8; i++) o.v[i] = FR_RADIX.one[i];
@@ -235,7 +236,7 @@ KZG_HD bool fr_is_zero(const fr& a) {
 KZG_HD fr fr_inv_binary(const fr& a) {
   uint32_t u[8], v[8], r[8], s[8];
   for (int i = 0; i < 8; i++) u[i] = FR_R[i], v[i] = a.v[i], r[i] = 0, s[i] = i == 0;
-  fr x = {{0, 0, 0, 0, 0, 0, 0, 0}};
+  fr x = fr_zero();
   bool reduced = fr_is_zero(a);  // x holds a^-1 2^(steps so far)
   auto halve = [](uint32_t (&w)[8]) {
     for (int i = 0; i < 8; i++) w[i] = (w[i] >> 1) | (i < 7 ? w[i + 1] << 31 : 0u);
@@ -298,7 +299,7 @@ KZG_HD fr fr_inv_binary(const fr& a) {
       t[8] = 0;
       fr rr;
       fr_cond_sub(rr, t);
-      fr_sub(x, fr{{0, 0, 0, 0, 0, 0, 0, 0}}, rr);
+      fr_sub(x, fr_zero(), rr);
       reduced = true;
     }
   }

@@ -73,7 +73,7 @@ int open_dev(const void* d_powers_of_g, const void* d_coeffs, uint64_t n, const 
     if ((e = launch_msm(false, bases, scalars, total, d_out, flags & KZGPOT_MSM_BASES_MONT,
                         p.c ? p.c : msm_window_bits(total), w + p.msm, key, s)))
       return e;
-    return launch_open_emit(values, (uint8_t*)d_out + kPointBytes, key, s);
+    return launch_fr_emit(values, (uint8_t*)d_out + kPointBytes, 16, key, s);  // value, random_v
   });
 }
 

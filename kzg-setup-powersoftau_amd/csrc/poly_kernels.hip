@@ -22,6 +22,9 @@
 // loop's trip count is a compile-time constant. No lane does more than 2 M <= 32 Horner steps and
 // 8 scan steps. Evaluate-only (no quotient) runs the up passes and the top level's down pass alone.
 //
+// The tree and the scan are poly_parts.hpp's block_tree and block_scan, the one place their steps
+// and barriers are stated; the kernels here pass the line that combines two values.
+//
 // Memory (the tile and its helpers are poly_parts.hpp's, shared with eval_kernels.hip): a lane's run
 // is M x 32 B at a stride of M x 32 B, so tiles are staged through LDS: every
 // global load and store is one uint4 per lane at consecutive addresses, and a lane reads its run
@@ -58,10 +61,10 @@ __device__ inline void run_sum(fr& acc, uint4* tile, bool raw, const fr& z) {
 #pragma unroll 1
   for (int k = G::M - 1; k >= 0; k--) {
     fr c;
-    tile_get(c, tile, s + 2 * k);
+    get_entry(c, tile, s + 2 * k);
     if (raw) {
       fr_load(c, c);
-      tile_put(tile, s + 2 * k, c);
+      put_entry(tile, s + 2 * k, c);
     }
     if (k == G::M - 1) acc = c;
     else mul_add(acc, acc, z, c);
@@ -75,32 +78,13 @@ __global__ void __launch_bounds__(256) k_poly_up(const uint4* __restrict__ in, u
   using G = Tile<T>;
   __shared__ uint4 tile[G::SLOTS];
   __shared__ uint32_t rows[8][256];
-  const uint32_t tid = threadIdx.x;
   stage_in<T>(tile, in, blockIdx.x, n_in);
   __syncthreads();
   fr acc;
   run_sum<T>(acc, tile, raw != 0, pw.p[0]);
-  park(rows, tid, acc);
   // a'[i] = a[2 i] + y a[2 i + 1], y = z^M, z^2M, ..: 128, 64, .. 1 live lanes
-#pragma unroll 1
-  for (int k = 0; k < 8; k++) {
-    const uint32_t live = 128u >> k;
-    __syncthreads();
-    fr lo, hi;
-    if (tid < live) {
-      unpark(lo, rows, 2 * tid);
-      unpark(hi, rows, 2 * tid + 1);
-    }
-    __syncthreads();
-    if (tid < live) {
-      mul_add(acc, hi, pw.p[G::LOG2M + k], lo);
-      park(rows, tid, acc);
-    }
-  }
-  if (tid == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) sums[(uint64_t)blockIdx.x * 8 + k] = acc.v[k];
-  }
+  block_tree(acc, rows, [&](fr& o, int k, const fr& lo, const fr& hi) { mul_add(o, hi, pw.p[G::LOG2M + k], lo); });
+  if (threadIdx.x == 0) words_out(sums + (uint64_t)blockIdx.x * 8, acc);
 }
 
 // ---------------------------------------------------------------- down: the H of one tile
@@ -119,45 +103,29 @@ __global__ void __launch_bounds__(256) k_poly_down(const uint4* in, uint64_t n_i
   stage_in<T>(tile, in, blk, n_in);
   __syncthreads();
   const fr z = pw.p[0];
-  fr acc, carry = {{0, 0, 0, 0, 0, 0, 0, 0}};
+  fr acc, carry = fr_zero();
   run_sum<T>(acc, tile, level0 != 0, z);
   if (tid == 255 && blk + 1 < gridDim.x) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) carry.v[k] = carries[(blk + 1) * 8 + k];
+    words_in(carry, carries + (blk + 1) * 8);
     mul_add(acc, carry, pw.p[G::LOG2M], acc);
   }
-  park(rows, tid, acc);
   // suffix scan: after step k lane l holds sum_{j < 2^(k+1)} y^j a[l + j], y = z^M
-#pragma unroll 1
-  for (int k = 0; k < 8; k++) {
-    const uint32_t d = 1u << k;
-    __syncthreads();
-    fr nb;
-    if (tid + d < 256) unpark(nb, rows, tid + d);
-    __syncthreads();
-    if (tid + d < 256) {
-      mul_add(acc, nb, pw.p[G::LOG2M + k], acc);
-      park(rows, tid, acc);
-    }
-  }
-  __syncthreads();
-  fr h = carry;  // lane 255: the tile's carry; the others: the next lane's suffix sum
-  if (tid < 255) unpark(h, rows, tid + 1);
+  block_scan(acc, rows, [&](fr& o, int k, const fr& a, const fr& nb) { mul_add(o, nb, pw.p[G::LOG2M + k], a); });
+  fr h = scan_neighbour(rows, carry);  // lane 255: the tile's carry; the others: the next lane's suffix sum
   const int s = (int)tid * G::RUN;
   fr o;
 #pragma unroll 1
   for (int k = G::M - 1; k >= 0; k--) {
     fr c;
-    tile_get(c, tile, s + 2 * k);
+    get_entry(c, tile, s + 2 * k);
     mul_add(h, h, z, c);
     o = h;
     if (level0) fr_store(o, h);
-    tile_put(tile, s + 2 * k, o);
+    put_entry(tile, s + 2 * k, o);
   }
   if (value && blk == 0 && tid == 0) {
     if (!level0) fr_store(o, h);
-#pragma unroll
-    for (int k = 0; k < 8; k++) value[k] = o.v[k];
+    words_out(value, o);
   }
   if (!out) return;
   __syncthreads();
@@ -170,10 +138,11 @@ __global__ void __launch_bounds__(256) k_poly_down(const uint4* in, uint64_t n_i
   }
 }
 
-__global__ void __launch_bounds__(64) k_open_emit(const uint32_t* __restrict__ values, uint32_t* __restrict__ out,
-                                                  const unsigned long long* __restrict__ key) {
+// an open's last step: `words` <= 64 words behind the proof's point, unless the call was rejected
+__global__ void __launch_bounds__(64) k_fr_emit(const uint32_t* __restrict__ values, uint32_t* __restrict__ out,
+                                                uint32_t words, const unsigned long long* __restrict__ key) {
   if (*key != ~0ull) return;
-  if (threadIdx.x < 16) out[threadIdx.x] = values[threadIdx.x];
+  if (threadIdx.x < words) out[threadIdx.x] = values[threadIdx.x];
 }
 
 // The up passes, then the down passes from the top: the levels are poly_plan's (plans.hpp)
@@ -209,17 +178,13 @@ hipError_t launch_poly_divide(const void* d_coeffs, uint64_t n, const fr_powers<
   const PolyPlan p = poly_plan(n, t);
   if (!p.bytes) return hipErrorInvalidValue;
   if (n == 0) return hipMemsetAsync(d_value, 0, 32, stream);  // the zero polynomial
-  switch (t) {
-    case 8: return launch<8>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);
-    case 9: return launch<9>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);
-    case 10: return launch<10>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);
-    case 11: return launch<11>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);
-    default: return launch<12>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream);
-  }
+  return with_tile<kPolyTileMin, kPolyTileMax>(
+      t, [&](auto T) { return launch<T()>(p, d_coeffs, z_pow, d_quotient, d_value, d_work, stream); });
 }
 
-hipError_t launch_open_emit(const void* d_values, void* d_out64, const unsigned long long* d_key, hipStream_t stream) {
-  hipLaunchKernelGGL(k_open_emit, dim3(1), dim3(64), 0, stream, (const uint32_t*)d_values, (uint32_t*)d_out64, d_key);
+hipError_t launch_fr_emit(const void* d_values, void* d_out, uint32_t words, const unsigned long long* d_key,
+                          hipStream_t stream) {
+  hipLaunchKernelGGL(k_fr_emit, dim3(1), dim3(64), 0, stream, (const uint32_t*)d_values, (uint32_t*)d_out, words, d_key);
   return hipGetLastError();
 }
 

@@ -4,7 +4,8 @@
 //   k_check_scalars  a block of 256 lanes owns 256 proofs, a lane one: rho_i, z_i, v_i and vbar_i are
 //                    any 256-bit integers, loaded as their residues. It writes the MSM's scalar rows
 //                    rho_i (row i) and rho_i z_i (row n + i), canonical, and the block's shares of
-//                    sum rho_i v_i and sum rho_i vbar_i (block_sum, poly_parts.hpp)
+//                    sum rho_i v_i and sum rho_i vbar_i (block_sum; it and the entry accessors are
+//                    poly_parts.hpp's)
 //   k_check_sums     one block: the sums of the shares, negated, as the scalars of g and gamma_g
 //                    (rows 2 n and 2 n + 1)
 //   k_g1_negate      one lane: an ark G1 record -> the record of its negative (infinity stays)
@@ -18,12 +19,6 @@
 
 namespace kzgpot {
 namespace {
-
-__device__ inline void store_entry(uint4* v, uint64_t i, fr a) {  // Montgomery -> canonical, 32 B
-  fr_store(a, a);
-  v[2 * i] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
-  v[2 * i + 1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
 
 // random_vs may be null (no proof is hiding: every vbar_i is 0)
 __global__ void __launch_bounds__(256) k_check_scalars(const uint4* __restrict__ randomizers, const uint4* __restrict__ points,
