@@ -159,6 +159,63 @@ def test_batch_sizes(gpu, setup, batch, n):
         assert run_batch(gpu, vk, batch, n, hiding=False) is False  # the random_vs dropped
 
 
+def test_batch_beyond_256_share_blocks(gpu, setup, batch):
+    """n = 65,700: 257 blocks leave 257 shares of each sum, so k_check_sums' sum_entries takes a second
+    pass (shares 256 ...). The 300 honest openings 219 times over with fresh distinct randomizers; one
+    value changed at 0, at 65,535 / 65,536 (the last entry of block 255, the first of block 256: the last
+    share of the first pass and the first of the second) and at n - 1; several; one random_v in block 256."""
+    vk, t = setup[2], 219
+    n = 300 * t
+    assert n == 65700 and (n + 255) // 256 == 257
+    rng = random.Random(10)
+    rho = [1] + [rng.getrandbits(128) for _ in range(n - 1)]
+    rho[65535], rho[65536] = TOP, R + 5
+    assert len(set(rho)) == n
+    le = lambda vs: b"".join(v.to_bytes(32, "little") for v in vs)  # noqa: E731
+    comms, wits, points, rho = batch["comms"] * t, batch["wits"] * t, le(batch["points"]) * t, le(rho)
+    values, random_vs = batch["values"] * t, batch["random_vs"] * t
+
+    def run(values=values, random_vs=random_vs):
+        res = gpu.g1_kzg_batch_check(vk, comms, points, le(values), wits, le(random_vs), rho)
+        assert res.ret in (0, 1) and res.first_bad == -1
+        return res.ret == 1
+
+    def changed(vs, *at):
+        vs = list(vs)
+        for i in at:
+            vs[i] = (vs[i] + 1) % R
+        return vs
+
+    assert run() is True
+    for i in (0, 65535, 65536, n - 1):
+        assert run(values=changed(values, i)) is False, i
+    assert run(values=changed(values, 7, 40000, 65536, 65650)) is False
+    assert 65600 // 256 == 256 and batch["random_vs"][65600 % 300] != 0
+    assert run(random_vs=changed(random_vs, 65600)) is False
+    # none hiding: the non-hiding third alone, 657 times over, without random_vs
+    plain = [i for i in range(300) if not batch["random_vs"][i] and i % 3 == 0]
+    assert len(plain) == 100
+    pick = lambda recs: b"".join(recs[96 * i: 96 * i + 96] for i in plain) * 657  # noqa: E731
+    pvalues = [batch["values"][i] for i in plain] * 657
+    ppoints = le([batch["points"][i] for i in plain]) * 657
+    res = gpu.g1_kzg_batch_check(vk, pick(batch["comms"]), ppoints, le(pvalues), pick(batch["wits"]), None, rho)
+    assert (res.ret, res.first_bad) == (1, -1)
+    res = gpu.g1_kzg_batch_check(vk, pick(batch["comms"]), ppoints, le(changed(pvalues, 65536)), pick(batch["wits"]), None, rho)
+    assert (res.ret, res.first_bad) == (0, -1)
+
+
+def test_check_of_two_infinities(gpu, setup):
+    """C = W = infinity: both pairs of the product are skipped; accepted for the value 0 at any point, and
+    only for it"""
+    vk = setup[2]
+    inf = O.ark_g1_serialize(O.ARK_G1_ZERO)
+    for z in (0, 1, TAU, TOP):
+        assert gpu.kzg_check(vk, inf, z, 0, inf) is True
+        assert gpu.kzg_check(vk, inf, z, R, inf) is True
+        assert gpu.kzg_check(vk, inf, z, 1, inf) is False
+    assert gpu.kzg_check(vk, inf, 5, 0, inf, random_v=1) is False
+
+
 def test_batch_empty(gpu, setup):
     assert gpu.kzg_batch_check(setup[2], [], [], [], []) is True
     assert gpu.g1_kzg_batch_check(setup[2], b"", b"", b"", b"", None, b"").ret == 1
