@@ -75,9 +75,12 @@ KZG_DEV void jac_dbl(jac<fp>& p) {
 // 169 + 169 (or 91 + 169) products instead of 196 + 196 (105 + 196), and signed digits need no
 // borrowed multiple of p, so a difference is 13 subtractions and values stay below 4.5 p. The price
 // is headroom: a product operand must be balanced, so the lazy sums that feed one (E = 3A,
-// X3 = F - 2D, 2 (X3 - D)) are renormalised by the carry-chain-free f30_norm. B = balanced
+// 2 (X3 - D)) are renormalised by the carry-chain-free f30_norm. A difference that FOLLOWS a
+// product (X3 = E^2 - 2D; the mixed addition's H, r and X3) is a tail of that product's scan
+// (fp381.hpp f30_column): its digits come out balanced and need no f30_norm. B = balanced
 // (|d| <= 2^29 + 4). Digit, top-digit and value bounds of every step, and a bound set closed under
-// a ladder step: tests/f30_ladder_model.py, tests/test_f30_ladder.py.
+// a ladder step: tests/f30_tail_model.py, tests/test_f30_tail.py (tests/f30_ladder_model.py and
+// tests/test_f30_ladder.py prove the same for the forms without tails, which these replaced).
 // 3P from the affine base (x, w = 2y) is tpl-2007-bl with Z1 = 1 in W form: YYw = w^2 = 4 YY,
 // T = YYw^2 = 16 YYYY, E = 3 x YYw - MM (= 12 x YY - MM), U = (M + E)^2 - MM - EE - T,
 // X3 = 4 (x EE - YYw U), W3 = 2 Y3 = 8 w (U (T - U) - E EE), Z3 = 2E. The mixed addition's
@@ -94,11 +97,8 @@ KZG_DEV void jac_dbl_w(jac<f30>& p) {
   f30_mul3(e, a);
   f30_norm(e, e);              // E = 3A                     B
   f30_mul(p.z, p.y, p.z);      // Z3 = W Z                   B
-  f30_sqr(a, e);               // F = E^2                    B
-  f30_dbl(t, d);
-  f30_sub(t, a, t);            // F - 2D                     |d| < 3 * 2^29
-  f30_norm(p.x, t);            // X3                         B
-  f30_sub(t, p.x, d);          // X3 - D                     |d| < 2^30 + 4
+  f30_sqr<-2>(p.x, e, d);      // X3 = E^2 - 2D, one scan    B
+  f30_sub(t, p.x, d);          // X3 - D                     |d| <= 2^30
   f30_norm<1>(t, t);           // 2 (X3 - D)                 B
   f30_mul_addsqr(d, e, t, b);  // -W3 = E 2 (X3 - D) + B'^2  B
   f30_neg(p.y, d);             // W3                         B
@@ -121,11 +121,7 @@ KZG_DEV void jac_tpl_affine_w(jac<f30>& p) {
   f30_sqr(ee, e);                               // EE
   f30_add(s, m, e);
   f30_norm(s, s);
-  f30_sqr(s, s);                                // S2 = (M + E)^2
-  f30_sub(s, s, mm);
-  f30_norm(s, s);
-  f30_sub(s, s, ee);
-  f30_norm(s, s);
+  f30_sqr<-1, -1>(s, s, mm, ee);                // S2 - MM - EE, S2 = (M + E)^2, one scan
   f30_sub(s, s, t);
   f30_norm(u, s);                               // U = S2 - MM - EE - T   B
   f30_neg(n, u);
@@ -147,13 +143,9 @@ KZG_DEV void jac_madd_w(jac<f30>& p, Load&& load) {
     f30 x2, w2;
     load(x2, w2);
     f30_sqr(z1z1, p.z);
-    f30_mul(h, x2, z1z1);      // U2
-    f30_sub(h, h, p.x);
-    f30_norm(h, h);            // H = U2 - X1                B
+    f30_mul<-1>(h, x2, z1z1, p.x);   // H = U2 - X1, one scan      B
     f30_mul(t, w2, p.z);
-    f30_mul(t, t, z1z1);       // 2 S2
-    f30_sub(r, t, p.y);
-    f30_norm(r, r);            // r = 2 S2 - W1              B
+    f30_mul<-1>(r, t, z1z1, p.y);    // r = 2 S2 - W1, one scan    B
   }
   const bool z1zero = f30_is_zero<F30_ZK>(p.z);
   const bool same = !z1zero && f30_is_zero<F30_ZK>(h) && f30_is_zero<F30_ZK>(r);
@@ -173,12 +165,7 @@ KZG_DEV void jac_madd_w(jac<f30>& p, Load&& load) {
   f30_norm<2>(hh, hh);         // I = 4 HH                   B
   f30_mul(j, h, hh);           // J = H I
   f30_mul(hh, p.x, hh);        // V = X1 I
-  f30_sqr(t, r);               // r^2
-  f30_sub(t, t, j);
-  f30_sub(t, t, hh);
-  f30_norm(t, t);              // r^2 - J - V                B
-  f30_sub(t, t, hh);
-  f30_norm(t, t);              // X3 = r^2 - J - 2V          B
+  f30_sqr<-1, -2>(t, r, j, hh);  // X3 = r^2 - J - 2V, one scan  B
   f30_sub(hh, hh, t);
   f30_norm(hh, hh);            // V - X3                     B
   f30_norm<1>(r, r);           // 2r                         B

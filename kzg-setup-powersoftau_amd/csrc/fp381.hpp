@@ -529,11 +529,13 @@ KZG_DEV void fp_from_mont(Fe<Tr>& canon, const Fe<Tr>& a) {
 // fit one 64-bit accumulator, and a multiply is 169 + 169 mads instead of 196 + 196: 75.8 against
 // 67.9 G multiplies/s, 91 against 83.6 G squarings/s (tools/microbench/mont30s.hip,
 // profiles/r03_mont30_microbench.txt). The price is headroom — an operand digit may not exceed
-// ~2^29.5 — which a pure square-and-multiply chain never needs; the ladders renormalise the three
-// lazy sums per doubling that feed a product (f30_norm below). The G2 ladders stay on 14 x 28: their
+// ~2^29.5 — which a pure square-and-multiply chain never needs; the ladders renormalise the two
+// lazy sums per doubling that feed a product (f30_norm below; a difference that follows a product is a
+// tail of that product's scan instead, f30_column). The G2 ladders stay on 14 x 28: their
 // three-product reductions do not fit one int64 here. Bounds: tests/test_fp30.py (worst-case
 // columns for the actual digits of p, an exact model of the exponentiation's functions against
-// Python integers) and tests/f30_ladder_model.py (the ladders' forms and the conversions).
+// Python integers), tests/f30_ladder_model.py (the ladders' forms and the conversions) and
+// tests/f30_tail_model.py (the scans' tail forms and the ladders that run them).
 constexpr int N30 = 13;
 struct f30 {
   int32_t v[N30];
@@ -583,13 +585,23 @@ KZG_DEV int32_t sext30(uint32_t x) { return __builtin_amdgcn_sbfe((int32_t)x, 0,
 #define KZG_F30_L11(M) KZG_F30_L10(M), M(10)
 #define KZG_F30_L12(M) KZG_F30_L11(M), M(11)
 #define KZG_F30_L13(M) KZG_F30_L12(M), M(12)
-#define KZG_F30_RUN(n, T) \
-  if constexpr (Cnt == n) \
-    asm(KZG_F30_S##n(KZG_F30_##T) : [c] "+v"(c), [o] "=&s"(carry_out) : KZG_F30_L##n(KZG_F30_##T##_IN));
-#define KZG_F30_RUNS13(T) \
-  KZG_F30_RUN(1, T) KZG_F30_RUN(2, T) KZG_F30_RUN(3, T) KZG_F30_RUN(4, T) KZG_F30_RUN(5, T) KZG_F30_RUN(6, T) \
-  KZG_F30_RUN(7, T) KZG_F30_RUN(8, T) KZG_F30_RUN(9, T) KZG_F30_RUN(10, T) KZG_F30_RUN(11, T) KZG_F30_RUN(12, T) \
-  KZG_F30_RUN(13, T)
+// A run may end with W = 1 or 2 TAIL mads, a lane value times an inline constant (K0, K1 in
+// -16 ... 64, which VOP3 encodes in the instruction): the linear terms of f30_mul / f30_sqr's tail
+// forms, on the same accumulator in the same statement. A tail is two operands, like a product.
+#define KZG_F30_TS0
+#define KZG_F30_TS1 "v_mad_i64_i32 %[c], %[o], %[t0], %[k0], %[c]\n\t"
+#define KZG_F30_TS2 KZG_F30_TS1 "v_mad_i64_i32 %[c], %[o], %[t1], %[k1], %[c]\n\t"
+#define KZG_F30_TIN0
+#define KZG_F30_TIN1 , [t0] "v"(t[0]), [k0] "n"(K0)
+#define KZG_F30_TIN2 KZG_F30_TIN1, [t1] "v"(t[1]), [k1] "n"(K1)
+#define KZG_F30_RUN(n, T, W) \
+  if constexpr (Cnt == n)    \
+    asm(KZG_F30_S##n(KZG_F30_##T) KZG_F30_TS##W : [c] "+v"(c), [o] "=&s"(carry_out) : KZG_F30_L##n(KZG_F30_##T##_IN) KZG_F30_TIN##W);
+#define KZG_F30_RUNS12(T, W) \
+  KZG_F30_RUN(1, T, W) KZG_F30_RUN(2, T, W) KZG_F30_RUN(3, T, W) KZG_F30_RUN(4, T, W) KZG_F30_RUN(5, T, W) \
+  KZG_F30_RUN(6, T, W) KZG_F30_RUN(7, T, W) KZG_F30_RUN(8, T, W) KZG_F30_RUN(9, T, W) KZG_F30_RUN(10, T, W) \
+  KZG_F30_RUN(11, T, W) KZG_F30_RUN(12, T, W)
+#define KZG_F30_RUNS13(T, W) KZG_F30_RUNS12(T, W) KZG_F30_RUN(13, T, W)
 // c + x_0 y_0 + ... (Cnt products of two lane values); Cnt = 0: nothing. Zero: c is 0 and enters the first
 // mad as the inline constant, not through a register that a v_mov would have to clear (column 0: one
 // product, f30_mul_addsqr's two)
@@ -605,20 +617,37 @@ KZG_DEV int64_t mad_i64_run(const int32_t (&x)[13], const int32_t (&y)[13], int6
         : [c] "=&v"(c), [o] "=&s"(carry_out)
         : KZG_F30_L2(KZG_F30_VV_IN));
   } else {
-    KZG_F30_RUNS13(VV)
+    KZG_F30_RUNS13(VV, 0)
   }
   return c;
 }
-// c + m_0 p_0 + ... (Cnt products of a lane value and a wave-uniform constant)
-template <int Cnt>
-KZG_DEV int64_t mad_i64_run_k(const int32_t (&m)[13], const int32_t (&p)[13], int64_t c) {
-  static_assert(Cnt >= 0 && Cnt <= 13, "a statement takes 30 operands");
+// c + m_0 p_0 + ... (Cnt products of a lane value and a wave-uniform constant) + K0 t_0 + K1 t_1 (the
+// tails, K = 0: none)
+template <int Cnt, int K0 = 0, int K1 = 0>
+KZG_DEV int64_t mad_i64_run_k(const int32_t (&m)[13], const int32_t (&p)[13], int64_t c, const int32_t (&t)[2] = {0, 0}) {
+  static_assert(Cnt >= 0 && Cnt + (K0 != 0) + (K1 != 0) <= 14 && (K0 != 0 || K1 == 0), "a statement takes 30 operands");
+  static_assert(K0 >= -16 && K0 <= 64 && K1 >= -16 && K1 <= 64, "a tail's factor is an inline constant");
   [[maybe_unused]] uint64_t carry_out;
-  KZG_F30_RUNS13(VK)
+  if constexpr (K1 != 0) {
+    static_assert(Cnt >= 1, "an upper column");
+    KZG_F30_RUNS12(VK, 2)
+  } else if constexpr (K0 != 0) {
+    static_assert(Cnt >= 1, "an upper column");
+    KZG_F30_RUNS13(VK, 1)
+  } else {
+    KZG_F30_RUNS13(VK, 0)
+  }
   return c;
 }
 #undef KZG_F30_RUNS13
+#undef KZG_F30_RUNS12
 #undef KZG_F30_RUN
+#undef KZG_F30_TIN2
+#undef KZG_F30_TIN1
+#undef KZG_F30_TIN0
+#undef KZG_F30_TS2
+#undef KZG_F30_TS1
+#undef KZG_F30_TS0
 constexpr int F30_NV = 20;  // lane-by-lane products of one column: f30_mul_addsqr's column 12 has 13 + 7
 
 template <int I, int End, class F>
@@ -638,10 +667,10 @@ KZG_DEV int64_t f30_run(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], 
 }
 // acc + x_0 y_0 + ... + x_{NV-1} y_{NV-1} + m_0 p_0 + ... + m_{NK-1} p_{NK-1}: the x y products as one
 // run (halved when too long for one statement), then the m p products as another. Zero: acc is 0
-// (column 0, which has no m p product)
-template <int NV, int NK, bool Zero = false>
+// (column 0, which has no m p product). K0, K1, t: the column's tails, which end the m p run
+template <int NV, int NK, bool Zero = false, int K0 = 0, int K1 = 0>
 KZG_DEV int64_t f30_col(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], const int32_t (&m)[N30],
-                        const int32_t (&p)[N30], int64_t acc) {
+                        const int32_t (&p)[N30], int64_t acc, const int32_t (&t)[2] = {0, 0}) {
   static_assert(NV >= 0 && NV <= F30_NV && NK >= 0 && NK <= N30, "column");
   if constexpr (Zero) {
     static_assert(NK == 0, "column 0");
@@ -650,7 +679,7 @@ KZG_DEV int64_t f30_col(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], 
   constexpr int V0 = NV > 13 ? (NV + 1) / 2 : NV;
   acc = f30_run<0, V0>(x, y, acc);
   acc = f30_run<V0, NV - V0>(x, y, acc);
-  return mad_i64_run_k<NK>(m, p, acc);
+  return mad_i64_run_k<NK, K0, K1>(m, p, acc, t);
 }
 // the end of column I: m_I and its product (a lower column) or the output digit (an upper one), the carry
 template <int I>
@@ -667,15 +696,31 @@ KZG_DEV int64_t f30_col_end(int64_t acc, int32_t (&m)[N30], f30& r) {
 // Column I of a product whose NV lane-by-lane products the caller has put into x, y: the m_j p_{I-j}
 // products of the reduction join them, then the column's end. After column 2 N30 - 2 the carry is the
 // top digit.
-template <int I, int NV>
+// Tails (K0, t0), (K1, t1), K = 0: none: an upper column I takes K0 t0_k + K1 t1_k (k = I - N30) into its
+// sum before its digit is taken, and the top digit K0 t0_12 + K1 t1_12 (f30_top), so that the scan
+// returns the balanced digits of the product's integer + K0 val(t0) + K1 val(t1) — a linear
+// combination that follows a product costs one mad per tail and upper column instead of the
+// digit-wise form and its f30_norm. The lower columns, m_i and the product chains are the plain form's.
+template <int I, int NV, int K0 = 0, int K1 = 0>
 KZG_DEV int64_t f30_column(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV], int64_t acc, int32_t (&m)[N30],
-                           f30& r) {
+                           f30& r, const int32_t (&t0)[N30] = {}, const int32_t (&t1)[N30] = {}) {
   constexpr int j0 = I < N30 ? 0 : I - (N30 - 1), nk = (I < N30 ? I - 1 : N30 - 1) - j0 + 1;
   int32_t mm[N30], pp[N30];
 #pragma unroll
   for (int k = 0; k < nk; k++) mm[k] = m[j0 + k], pp[k] = P30[I - j0 - k];
-  acc = f30_col<NV, nk, I == 0>(x, y, mm, pp, acc);
+  if constexpr (I < N30 || K0 == 0) {
+    acc = f30_col<NV, nk, I == 0>(x, y, mm, pp, acc);
+  } else {
+    const int32_t t[2] = {t0[I - N30], t1[I - N30]};
+    acc = f30_col<NV, nk, false, K0, K1>(x, y, mm, pp, acc, t);
+  }
   return f30_col_end<I>(acc, m, r);
+}
+template <int K0, int K1>
+KZG_DEV int32_t f30_top(int64_t acc, const f30& t0, const f30& t1) {
+  if constexpr (K0 == 0) return (int32_t)acc;
+  else if constexpr (K1 == 0) return (int32_t)acc + K0 * t0.v[N30 - 1];
+  else return (int32_t)acc + K0 * t0.v[N30 - 1] + K1 * t1.v[N30 - 1];
 }
 // r = a b 2^-390 mod p for balanced a, b (|digit| <= 2^29, |top digit| <= 2^23: the bound
 // tests/test_fp30.py proves, TOP_IN = 2^23 + 1, and the exponentiation's callers use); r balanced with
@@ -685,7 +730,10 @@ KZG_DEV int64_t f30_column(const int32_t (&x)[F30_NV], const int32_t (&y)[F30_NV
 // tests/test_fp30.py (the sum started at +2^29, digit (acc & M30) - 2^29, carry acc >> 30), an
 // instruction fewer per column where the bias is no chain's free start addend. Every partial sum is
 // bounded by the sum of absolute values those tests prove, in any order of accumulation.
-KZG_DEV void f30_mul(f30& r, const f30& a, const f30& b) {
+// Tail form f30_mul<K0[, K1]>(r, a, b, t0[, t1]): the balanced digits of the plain form's integer
+// + K0 val(t0) + K1 val(t1) (f30_column; any int32 digits in t; bounds: tests/f30_tail_model.py).
+template <int K0 = 0, int K1 = 0>
+KZG_DEV void f30_mul(f30& r, const f30& a, const f30& b, const f30& t0 = f30{}, const f30& t1 = f30{}) {
   KZG_FPOP(FpOp::Mul30);
   constexpr int N = N30;
   int32_t m[N];
@@ -697,12 +745,13 @@ KZG_DEV void f30_mul(f30& r, const f30& a, const f30& b) {
 #pragma unroll
     for (int j = 0; j < n; j++) x[j] = a.v[j0 + j], y[j] = b.v[i - j0 - j];
     if constexpr (i < N) x[n] = a.v[i], y[n] = b.v[0];
-    acc = f30_column<i, n + (i < N)>(x, y, acc, m, r);
+    acc = f30_column<i, n + (i < N), K0, K1>(x, y, acc, m, r, t0.v, t1.v);
   });
-  r.v[N - 1] = (int32_t)acc;
+  r.v[N - 1] = f30_top<K0, K1>(acc, t0, t1);
 }
-// r = a^2 2^-390: cross products once as a_j (2 a_k), the same reduction
-KZG_DEV void f30_sqr(f30& r, const f30& a) {
+// r = a^2 2^-390: cross products once as a_j (2 a_k), the same reduction, the same tail form
+template <int K0 = 0, int K1 = 0>
+KZG_DEV void f30_sqr(f30& r, const f30& a, const f30& t0 = f30{}, const f30& t1 = f30{}) {
   KZG_FPOP(FpOp::Sqr30);
   constexpr int N = N30;
   int32_t d[N], m[N];
@@ -717,9 +766,9 @@ KZG_DEV void f30_sqr(f30& r, const f30& a) {
 #pragma unroll
     for (int j = 0; j < nc; j++) x[j] = a.v[j0 + j], y[j] = d[i - j0 - j];
     if constexpr (sq) x[nc] = y[nc] = a.v[i / 2];
-    acc = f30_column<i, nc + sq>(x, y, acc, m, r);
+    acc = f30_column<i, nc + sq, K0, K1>(x, y, acc, m, r, t0.v, t1.v);
   });
-  r.v[N - 1] = (int32_t)acc;
+  r.v[N - 1] = f30_top<K0, K1>(acc, t0, t1);
 }
 // ---- the forms the G1 subgroup ladders need (curve.hpp, jac<f30>). Operand discipline, proven by
 // tests/f30_ladder_model.py for every call site: a "balanced" value (B) has lower digits

@@ -9,7 +9,9 @@ per-wave dynamic count of each instruction class is (static count in each loop b
 count) + (straight-line code, run once). This tool disassembles the library, finds the loops
 (back-edges, including the s_getpc / s_setpc far jumps), classifies them by their body (radix-2^30
 squaring: 260 v_mad_i64_i32; window step: the table lookup + f30 multiply; ladder doubling:
->= 1,500 v_mad_u64_u32 (G2) or v_mad_i64_i32 (G1, 13 x 30 ladders) in a loop with no LDS), and prints the per-site table as JSON, with the
+>= 1,500 v_mad_u64_u32 (G2) or v_mad_i64_i32 (G1, 13 x 30 ladders) in a loop with no LDS; the mixed
+addition: the loop around the doubling loop whose own part fetches the base point from LDS, run once
+per set bit of |u| below its two leading bits, which the tripling consumes), and prints the per-site table as JSON, with the
 PMC per-wave counts beside it when a stall profile (tools/codec_stall_summary.py output) is given.
 
     python3 tools/isa_sites.py [--lib kzg-setup-powersoftau_amd/build/libkzgpot.so]
@@ -113,6 +115,14 @@ def sqrt_schedule():
     return len(sq) - 1, sum(sq[1:])  # window steps after the first, squarings in them
 
 
+def ladder_schedule():
+    """(doublings, mixed additions) of one [|u|] ladder after the tripling of its two leading bits"""
+    text = open(os.path.join(ROOT, "kzg-setup-powersoftau_amd", "csrc", "bls12_381_consts.hpp")).read()
+    u = int(re.search(r"BLS_ABS_U = (0x[0-9a-fA-F]+)", text).group(1), 16)
+    low = u & ((1 << (u.bit_length() - 2)) - 1)
+    return u.bit_length() - 2, bin(low).count("1")
+
+
 def attribute(ins, kernel):
     """Loops of the hot path with their trip counts, exclusive counts (nested loops removed)."""
     loops = sorted({(t, off) for off, op, _, t in ins if t is not None and t <= off and cat(op) == "branch"})
@@ -120,12 +130,14 @@ def attribute(ins, kernel):
     # each exponentiation is inlined where it is called (G2: two copies), so a copy's loops run the
     # schedule once per wave; G1's two [|u|] ladders share ONE copy of the ladder code
     ladders = 2 if kernel == "k_g1_codec" else 1
+    doublings, additions = ladder_schedule()
     sites = []
     for lo, hi in loops:
         nested = [(a, b) for a, b in loops if lo <= a and b <= hi and (a, b) != (lo, hi)]
         c, m = counts(ins, lo, hi, nested)
         call, mall = counts(ins, lo, hi)
-        sites.append({"lo": lo, "hi": hi, "bytes": hi - lo + 4, "nested": len(nested), "excl": c, "mads": mall})
+        sites.append({"lo": lo, "hi": hi, "bytes": hi - lo + 4, "nested": len(nested), "excl": c, "mads": mall,
+                      "excl_mads": m, "inner": nested})
     out = []
     # radix-2^30 squaring loops (260 i64 mads, nothing nested): the one inside the window loop runs
     # the schedule's squarings; one outside it, the table's a^240 (4 iterations)
@@ -143,10 +155,21 @@ def attribute(ins, kernel):
             s["trips_per_wave"] = steps
         elif s["nested"] == 0 and max(u64, i64) >= 1500 and s["excl"].get("lds", 0) == 0 and s["excl"].get("smem", 0) == 0:
             s["site"] = "ladder: doubling loop (jac_dbl_w, bit test, back-edge)"
-            s["trips_per_wave"] = ladders * 62
+            s["trips_per_wave"] = ladders * doublings
         else:
             continue
         out.append(s)
+    # the mixed addition: the innermost loop around the fast ladder's doubling loop. Its own part (the
+    # doubling loop taken out) reads the parked base point from LDS and holds the addition's
+    # reductions; the cold copy of the doubling for the equal-point branch lies in a loop further out
+    for d in [s for s in out if s["site"].startswith("ladder")]:
+        around = [s for s in sites if s["inner"] == [(d["lo"], d["hi"])] and s["excl"].get("lds", 0) > 0
+                  and max(s["excl_mads"].get("v_mad_i64_i32", 0), s["excl_mads"].get("v_mad_u64_u32", 0)) >= 1500]
+        if around:
+            s = min(around, key=lambda x: x["hi"] - x["lo"])
+            s["site"] = "mixed addition: the loop around the ladder's doubling loop (jac_madd_w, base point from LDS)"
+            s["trips_per_wave"] = ladders * additions
+            out.append(s)
     # de-duplicate loop records that share a body (several back-edges into one header): keep the
     # innermost per site and header
     seen, res = set(), []
@@ -182,9 +205,10 @@ def main():
                          "trips_per_wave": s["trips_per_wave"],
                          "static_per_trip": {k: s["excl"].get(k, 0) for k in classes if s["excl"].get(k, 0)},
                          "per_wave": {k: v for k, v in d.items() if v}})
-        # code outside the hot loops: the straight-line prologue / emit / ladder additions and the cold
-        # paths. Its hot part runs once per wave (the 4 mixed additions 4 times): an upper bound on
-        # its per-wave share is its static count (cold branches included)
+        # code outside the attributed sites: the straight-line prologue / emit / tripling and the cold
+        # paths (the equal-point branch's copy of the doubling among them). Its hot part runs once
+        # per wave (the tripling once per ladder): an upper bound on its per-wave share is its static
+        # count (cold branches included)
         outside = collections.Counter()
         for off, op, _, _ in ins:
             if not any(lo <= off <= hi for lo, hi in loop_ranges):
